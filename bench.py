@@ -4,10 +4,14 @@
 step mix) on N MI355X GPUs of one node.
 
     python bench.py --gpus 1 --steps 30 --warmup 6
+    python bench.py --gpus 1 --steps 30 --warmup 6 --full             # + every secondary measurement below
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
-Prints ONE JSON line on rank 0 (see the field notes in DESIGN.md section "Measurement").
+Prints ONE JSON line on rank 0 (see the field notes in DESIGN.md section "Measurement").  A plain run sets up, warms
+up, times the K steps and prints the line; `--full` adds what the headline does not need: the per-rank exchange times
+(`config.rank_times`), the profiled passes (`roofline`, `kernel_classes`), the other configurations (`secondary`) and the
+CPU baseline (`cpu_baseline`).  `--dump-outputs DIR` writes what the last timed step computed as DIR/<name>.npy.
 """
 import argparse
 import json
@@ -321,6 +325,39 @@ def project_eight_ranks(gen_ms, disc_ms, sec, link_gbps=76.8):
     return out
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, model, last):
+    """What the last timed step computed, as a caller of OTGAN.step holds it afterwards: the step's matching distance and
+    entropy, and the weights it left behind (the generator's and the critic's trainable variables, in creation order, and
+    the generator's EMA shadows), each flattened to one float32 array.  Arrays are read after the timed window has been
+    synchronised, so nothing here is timed.  If the arrays together exceed DUMP_LIMIT_BYTES, each weight array is cut to the
+    same fraction of its elements by a fixed sample of positions (NumPy seed 0, sorted), the same from run to run."""
+    import numpy as np
+    import torch
+
+    def flat(ts):
+        return torch.cat([t.detach().reshape(-1).float() for t in ts]).cpu().numpy()
+
+    arrays = {"distance": flat([torch.as_tensor(last["distance"])]),
+              "entropy": flat([torch.as_tensor(last["entropy"])]),
+              "generator_weights": flat(model.gen_params),
+              "critic_weights": flat(model.disc_params),
+              "generator_ema_weights": flat([model.ema.average(p) for p in model.gen_params])}
+    total = sum(v.nbytes for v in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        # the scalars stay whole; the weight arrays share what is left of the limit
+        big = {k: v for k, v in arrays.items() if v.size > 1}
+        frac = (DUMP_LIMIT_BYTES - (total - sum(v.nbytes for v in big.values()))) / sum(v.nbytes for v in big.values())
+        for k, v in big.items():
+            idx = np.sort(np.random.RandomState(0).choice(v.size, int(v.size * frac), replace=False))
+            arrays[k] = v[idx]
+    os.makedirs(out_dir, exist_ok=True)
+    for k, v in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), np.ascontiguousarray(v, dtype=np.float32))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -331,10 +368,16 @@ def main():
     ap.add_argument("--nr_sinkhorn_iter", type=int, default=100)
     ap.add_argument("--matching_scope", type=str, default="global")
     ap.add_argument("--image_size", type=int, default=32)
-    ap.add_argument("--no_cpu_baseline", action="store_true")
-    ap.add_argument("--no_prof", action="store_true", help="skip the second (profiled) pass that feeds `roofline`")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the measurements beside the headline: per-rank exchange times, the profiled passes "
+                         "(`roofline`), the secondary configurations and the CPU baseline (off by default)")
+    ap.add_argument("--no_cpu_baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no_prof", action="store_true", help="with --full: skip the second (profiled) pass that feeds `roofline`")
     ap.add_argument("--no_secondary", action="store_true",
-                    help="skip the secondary measurements (matching block alone, DenseNet cfg4 shape, 64x64 cfg5 shape)")
+                    help="with --full: skip the secondary measurements (matching block alone, DenseNet cfg4 shape, 64x64 cfg5 shape)")
+    ap.add_argument("--dump-outputs", dest="dump_outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (distance, entropy, the updated "
+                         "generator / critic / EMA weights) as DIR/<name>.npy in float32")
     a = ap.parse_args()
 
     import torch
@@ -412,11 +455,13 @@ def main():
         t = torch.tensor([dt], dtype=torch.float64, device="cpu" if torch.distributed.get_backend() == "gloo" else dev)
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
         dt = float(t.item())
-    # ---- pass 1b (ranks > 1 only; never mixed into `value`): the same K steps with the exchange regions of the step
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, model, last)
+    # ---- pass 1b (--full, ranks > 1 only; never mixed into `value`): the same K steps with the exchange regions of the step
     # bracketed by events on every rank's compute stream (trainer.enable_timers): per-rank matching / all-gather / all-reduce
     # milliseconds per step, so that a first real scaling curve can be read (what grows with the rank count is there)
     rank_times = None
-    if world > 1 or model.collectives:
+    if a.full and (world > 1 or model.collectives):
         model.enable_timers(True)
         model.step_counter = 0
         parallel.barrier()
@@ -434,14 +479,14 @@ def main():
             rank_times = allt
         else:
             rank_times = [mine]
-    # ---- pass 2 (feeds `roofline` / `kernel_classes` only): the same K steps with every library launch
+    # ---- pass 2 (--full; feeds `roofline` / `kernel_classes` only): the same K steps with every library launch
     # bracketed by HIP events on its launch stream (otgan_prof_*).  Never mixed into `value`.
     # Two sub-passes since the step runs on two streams (round 5): (2a) the schedule of the headline pass -- the GEMM's
     # launches overlap HBM-bound transform kernels of the other stream, so their event-bracketed durations are those of a
     # kernel SHARING the device (reported as `roofline.two_stream`); (2b) the same K steps with the second stream off: every
     # launch has the device to itself, which is what a kernel-vs-pipe roofline means (`roofline.achieved` / `frac`).
     prof, dt_prof, prof_ovl, dt_ovl = None, None, None, None
-    if not a.no_prof:
+    if a.full and not a.no_prof:
         def _prof_pass():
             _lib.prof_reset()
             _lib.prof_enable(True)
@@ -526,7 +571,7 @@ def main():
                                  for k, v in prof.items() if v["launches"]}
         # wino_gemm launches are nested inside the conv classes: not added again
         out["kernel_time_frac_of_wall"] = round(sum(v["ms"] for k, v in prof.items() if not k.startswith("wino_gemm")) / (dt_prof * 1e3), 4)
-    if world == 1 and not a.no_secondary:
+    if a.full and world == 1 and not a.no_secondary:
         model.close()
         del model, x
         torch.cuda.empty_cache()
@@ -552,7 +597,7 @@ def main():
                             "MFMAs per product; everything else identical; own process, unprofiled"}
             except Exception as e:      # never lose the headline line over the reference point
                 out["secondary"]["three_bf16_pieces_24bit"] = {"error": repr(e)[:200]}
-    if world == 1 and not a.no_cpu_baseline:
+    if a.full and world == 1 and not a.no_cpu_baseline:
         from oracle import train_step_cpu
         # bounded sample: 2 shards x 16 images (~10 s of CPU work), at most 32 host threads (torch's CPU convs
         # degrade badly when oversubscribed: 256 threads took >4 min for this sample)

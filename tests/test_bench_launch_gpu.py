@@ -22,7 +22,7 @@ def _env(**kw):
 
 def test_bench_gpus2_self_launches_two_ranks():
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "6", "--warmup", "1",
-                        "--no_cpu_baseline", "--no_secondary", "--no_prof"],
+                        "--full", "--no_cpu_baseline", "--no_secondary", "--no_prof"],
                        env=_env(OTGAN_SINGLE_DEVICE="1"), capture_output=True, text=True, timeout=1500)
     assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-4000:])
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]

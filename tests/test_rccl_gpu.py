@@ -44,7 +44,7 @@ def test_bench_runs_with_forced_collectives():
     """bench.py --gpus 1 with every collective of the step going through RCCL (async all-gather of the real
     features overlapping the generator forward, bucketed gradient all-reduce under the backward pass)."""
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "6", "--warmup", "2",
-                        "--no_cpu_baseline", "--no_secondary", "--batch_per_gpu", "64", "--nr_sinkhorn_iter", "20"],
+                        "--full", "--no_cpu_baseline", "--no_secondary", "--batch_per_gpu", "64", "--nr_sinkhorn_iter", "20"],
                        env=_env(), capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-4000:])
     line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])

@@ -3,7 +3,7 @@
 #   tools/debug/ab_env.sh "OTGAN_X3_NARROW=0" "OTGAN_X3_NARROW=1" ...   (extra bench flags in BENCH_FLAGS)
 cd ${GRAFT_REPO_ROOT:-.}
 for setting in "$@" "$1"; do
-  line=$(env $setting python bench.py --steps 36 --warmup 6 --no_cpu_baseline --no_secondary ${BENCH_FLAGS} 2>/dev/null | grep '^{' | tail -1)
+  line=$(env $setting python bench.py --full --steps 36 --warmup 6 --no_cpu_baseline --no_secondary ${BENCH_FLAGS} 2>/dev/null | grep '^{' | tail -1)
   python - "$setting" "$line" <<'PY'
 import json, sys
 d = json.loads(sys.argv[2])
