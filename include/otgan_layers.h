@@ -409,4 +409,45 @@ int otgan_nesterov_step_f32(float* p, const float* grad, float* v, long n, doubl
 /* shadow = decay*shadow + (1-decay)*p */
 int otgan_ema_update_f32(float* shadow, const float* p, long n, double decay, void* stream);
 
+/*
+ * Inception-v3 inference (the 2015 graph of the reference's evaluation, utils/inception.py; lowered by
+ * utils/inception_net.py).  NHWC fp32 activations, HWIO fp32 weights, fp32 MFMA with exact fp32 products.  Any
+ * spatial size; padding the TensorFlow way: VALID -> out = (in - k) / s + 1; SAME -> out = ceil(in / s), pad_before =
+ * max((out - 1) * s + k - in, 0) / 2.  None of these calls needs a workspace.
+ */
+typedef struct otgan_incep_conv_desc {
+  int N, H, W;     /* batch, input spatial size */
+  int C, ldx;      /* input channels, channel stride of the input buffer (>= C) */
+  int KH, KW;      /* taps */
+  int stride_h, stride_w;
+  int same;        /* 1: TF 'SAME' padding, 0: 'VALID' */
+  int Cout;        /* output channels, a multiple of 4 */
+  int ldy, y_coff; /* output written at channel offset y_coff of a buffer with channel stride ldy */
+  int relu;        /* 1: y = max(conv + bias, 0) */
+} otgan_incep_conv_desc;
+
+#define OTGAN_INCEP_POOL_MAX 0
+#define OTGAN_INCEP_POOL_AVG 1 /* divides by the number of in-bounds taps (TF) */
+typedef struct otgan_incep_pool_desc {
+  int N, H, W, C, ldx;
+  int KH, KW, stride_h, stride_w, same;
+  int op;          /* OTGAN_INCEP_POOL_* */
+  int ldy, y_coff;
+} otgan_incep_pool_desc;
+
+/* output size of one spatial dimension (-1 for bad arguments) */
+int otgan_incep_out_size(int in, int k, int stride, int same);
+/* y[n, oh, ow, y_coff + co] = act(bias[co] + sum x[n, ih, iw, ci] w[kh][kw][ci][co]); bias nullable; w 16-byte aligned */
+int otgan_incep_conv2d_f32(const otgan_incep_conv_desc* d, const float* x, const float* w, const float* bias, float* y,
+                           void* stream);
+int otgan_incep_pool_f32(const otgan_incep_pool_desc* d, const float* x, float* y, void* stream);
+/* y [N, OH, OW, C] (dense) = scale * bilinear(x [N, H, W, C]) + shift; TF's legacy mapping (no half-pixel offset):
+ * src = dst * in / out, or dst * (in - 1) / (out - 1) with align_corners; upper neighbour clamped to the edge */
+int otgan_incep_resize_f32(int N, int H, int W, int C, int OH, int OW, int align_corners, float scale, float shift,
+                           const float* x, float* y, void* stream);
+/* pool3 [N, C] = mean of the HW pixels of x (channel stride ldx); logits [N, classes] = pool3 . w (w: [C][classes],
+ * no bias); probs = row softmax of logits.  C and classes multiples of 4, pool3 16-byte aligned. */
+int otgan_incep_head_f32(int N, int HW, int C, int ldx, int classes, const float* x, const float* w, float* pool3,
+                         float* logits, float* probs, void* stream);
+
 #endif /* OTGAN_LAYERS_H */

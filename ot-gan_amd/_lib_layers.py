@@ -21,6 +21,23 @@ class ConvDesc(ctypes.Structure):
 P_DESC = ctypes.POINTER(ConvDesc)
 
 
+class IncepConvDesc(ctypes.Structure):
+    """Mirror of `otgan_incep_conv_desc`."""
+    _fields_ = [("N", c_int), ("H", c_int), ("W", c_int), ("C", c_int), ("ldx", c_int), ("KH", c_int), ("KW", c_int),
+                ("stride_h", c_int), ("stride_w", c_int), ("same", c_int), ("Cout", c_int), ("ldy", c_int),
+                ("y_coff", c_int), ("relu", c_int)]
+
+
+class IncepPoolDesc(ctypes.Structure):
+    """Mirror of `otgan_incep_pool_desc`."""
+    _fields_ = [("N", c_int), ("H", c_int), ("W", c_int), ("C", c_int), ("ldx", c_int), ("KH", c_int), ("KW", c_int),
+                ("stride_h", c_int), ("stride_w", c_int), ("same", c_int), ("op", c_int), ("ldy", c_int),
+                ("y_coff", c_int)]
+
+
+INCEP_POOL_MAX, INCEP_POOL_AVG = 0, 1
+
+
 class Dense16BwdPair(ctypes.Structure):
     """Mirror of `otgan_dense16_bwd_pair`."""
     _fields_ = [("w", ctypes.c_void_p), ("fwd_filters", ctypes.c_void_p), ("filters", ctypes.c_void_p),
@@ -99,4 +116,9 @@ SIGNATURES = {
     "otgan_adamax_step_f32": (c_int, [c_fp, c_fp, c_fp, c_fp, c_long, c_double, c_double, c_double, c_fp]),
     "otgan_nesterov_step_f32": (c_int, [c_fp, c_fp, c_fp, c_long, c_double, c_double, c_fp]),
     "otgan_ema_update_f32": (c_int, [c_fp, c_fp, c_long, c_double, c_fp]),
+    "otgan_incep_out_size": (c_int, [c_int, c_int, c_int, c_int]),
+    "otgan_incep_conv2d_f32": (c_int, [ctypes.POINTER(IncepConvDesc), c_fp, c_fp, c_fp, c_fp, c_fp]),
+    "otgan_incep_pool_f32": (c_int, [ctypes.POINTER(IncepPoolDesc), c_fp, c_fp, c_fp]),
+    "otgan_incep_resize_f32": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_float, c_fp, c_fp, c_fp]),
+    "otgan_incep_head_f32": (c_int, [c_int, c_int, c_int, c_int, c_int, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp]),
 }

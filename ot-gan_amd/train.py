@@ -11,7 +11,7 @@ physical GPUs (= torch.distributed world size): every rank owns nr_gpu / world s
 Added flags (not in the reference): --synthetic (random CIFAR-shaped data instead of the
 pickled dataset), --synthetic_size, --matching_scope global|local, --max_steps, --image_size, --save_every,
 --data_dependent_init, --eval_every / --eval_samples / --inception_model (the reference's Inception-score hook,
-train.py:245-272, with the classifier as an input: there is no network to download the 2015 graph).
+train.py:245-272: --inception_model takes the reference's own 2015 graph file, or a TorchScript classifier).
 
 Checkpoints (`<save_dir>/med_gan_params-<epoch>`, the reference's naming, train.py:275-277) are torch pickles
 of {variable name: tensor} plus optimiser moments / step count and EMA shadows (which the reference's
@@ -64,8 +64,9 @@ def build_parser():
     p.add_argument('--eval_every', type=int, default=100, help='Inception score every this many epochs (reference: 100, train.py:245)')
     p.add_argument('--eval_samples', type=int, default=50000, help='samples per score (reference: 50000, train.py:262)')
     p.add_argument('--inception_model', type=str, default='',
-                   help='TorchScript classifier (float32 images [n,H,W,3] in 0..255 -> class probabilities); without it the '
-                        'Inception-score hook is skipped (the reference downloads the 2015 Inception graph)')
+                   help="the reference's 2015 Inception graph (classify_image_graph_def.pb, inception-2015-12-05.tgz or the "
+                        'directory holding the .pb; runs on the GPU kernels) or a TorchScript classifier (float32 images '
+                        '[n,H,W,3] in 0..255 -> class probabilities); without it the Inception-score hook is skipped')
     p.add_argument('--step_graph', type=int, nargs='?', const=1, default=None, choices=(0, 1),
                    help='replay whole steps as hipGraphs after the first period (single-process runs; bit-identical to the '
                         'eager steps).  Default: on for --model densenet (launch-bound: replay 25.5 ms against 27.6 - 29.6 ms), '
@@ -80,15 +81,23 @@ def inception_hook(model, args, classifier, state, rank=0, world=1):
     samples and scores 2 x 50 000 images.  All ranks get the same scores; rank 0 prints them."""
     from .utils.inception import class_probabilities, inception_score_from_probs
     from . import parallel
+    on_device = hasattr(classifier, "probs_from_generator")    # utils.inception_net.InceptionNet: samples stay on the GPU
     share = -(-args.eval_samples // world)
     out = {}
     for tag, ema in (("", False), ("EMA ", True)):
         probs, have = [], 0
         while have < share:
-            x = model.sample(min(1000, share - have), ema=ema).float().cpu().numpy()
-            probs.append(class_probabilities([127.5 * (im + 1.) for im in x], classifier))   # train.py:260-262
+            x = model.sample(min(1000, share - have), ema=ema)
+            if on_device:
+                probs.append(classifier.probs_from_generator(x.float()))                      # 127.5 (x + 1) folded in
+            else:
+                x = x.float().cpu().numpy()
+                probs.append(class_probabilities([127.5 * (im + 1.) for im in x], classifier))   # train.py:260-262
             have += x.shape[0]
-        p = torch.from_numpy(np.concatenate(probs)[:share].astype(np.float32)).to(model.device)
+        if on_device:
+            p = torch.cat(probs)[:share].float().to(model.device)
+        else:
+            p = torch.from_numpy(np.concatenate(probs)[:share].astype(np.float32)).to(model.device)
         p = parallel.all_gather_rows(p)[:args.eval_samples].cpu().numpy()
         score = inception_score_from_probs(p, splits=10)
         if rank == 0:

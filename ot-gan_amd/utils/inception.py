@@ -33,7 +33,26 @@ def inception_score_from_probs(preds, splits=10):
 
 
 def load_classifier(path, device="cpu"):
-    """A TorchScript module mapping float32 images [n, H, W, 3] in 0..255 to class probabilities, as a callable."""
+    """The classifier in `path`, dispatched on the file's content:
+    * a zip archive is a TorchScript module mapping float32 images [n, H, W, 3] in 0..255 to class probabilities,
+      returned as a numpy callable;
+    * anything else is the reference's 2015 Inception graph -- `classify_image_graph_def.pb`, the
+      `inception-2015-12-05.tgz` it comes in, or a directory holding the .pb -- returned as a device
+      `utils.inception_net.InceptionNet` on `device` (a numpy callable too, and `probs` / `pool3` /
+      `probs_from_generator` on CUDA tensors)."""
+    import os
+    import zipfile
+    if not os.path.isdir(path) and zipfile.is_zipfile(path):
+        return _load_torchscript(path, device)
+    from .inception_net import InceptionNet
+    try:
+        return InceptionNet(path, device)
+    except (OSError, ValueError, KeyError, IndexError) as e:
+        raise ValueError("%s is neither a TorchScript archive (zip) nor the 2015 Inception graph (%s, its .tgz, or a "
+                         "directory holding it): %s" % (path, "classify_image_graph_def.pb", e)) from e
+
+
+def _load_torchscript(path, device):
     import torch
     mod = torch.jit.load(path, map_location=device).eval()
 
