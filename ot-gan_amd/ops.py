@@ -120,9 +120,13 @@ def _epoch_of(t):
     return _storage_epoch.get(t.untyped_storage().data_ptr(), 0)
 
 
+def _token(V, g):
+    return (weights_epoch, _epoch_of(V), _epoch_of(g), V._version, g._version)
+
+
 def cached_weights(V, g, compute):
     key = id(V)
-    token = (weights_epoch, _epoch_of(V), _epoch_of(g), V._version, g._version)
+    token = _token(V, g)
     hit = _wcache.get(key)
     if hit is not None and hit[0] is V and hit[1] is g and hit[2] == token:
         _wcache.move_to_end(key)
@@ -133,6 +137,57 @@ def cached_weights(V, g, compute):
     while len(_wcache) > _WCACHE_MAX:      # evict the least recently used entry only
         _wcache.popitem(last=False)
     return val
+
+
+def weights_in(t):
+    """The weight-cache entries of the parameters in `t`'s storage and the dense-block operands made from them, as they
+    stand: a snapshot for reinstate_weights() (trainer.GraphedSteps keeps the ones its "gen1" capture made)."""
+    key = t.untyped_storage().data_ptr()
+    ents = [(k, e[0], e[1], e[3]) for k, e in _wcache.items() if e[0].untyped_storage().data_ptr() == key]
+    mine = {id(e[3][0]) for e in ents}
+    blocks = [(k, e) for k, e in _block_cache.items() if e[0] and all(id(w) in mine for w in e[0])]
+    return ents, blocks
+
+
+def forget_weights(t):
+    """Drop the cache entries of the parameters in `t`'s storage (a trainer that is closed: its entries -- normalised
+    weights and Winograd filters, 100+ MB for a wide layer -- would otherwise stay until 1024 newer entries evict them)."""
+    ents, blocks = weights_in(t)
+    for k, *_ in ents:
+        _wcache.pop(k, None)
+    for k, _e in blocks:
+        _block_cache.pop(k, None)
+
+
+def forget_stream(stream):
+    """Drop the workspace of a stream that is no longer used."""
+    for key in [k for k in _ws if k[1] == stream.cuda_stream]:
+        del _ws[key]
+
+
+def forget_side_events():
+    """A step capture has ended (trainer.GraphedSteps): drop the events that ordered input-gradient filters made on the side
+    stream (Conv2dFunction.forward) before their use.  An event recorded inside a capture has no meaning outside it, and
+    nothing outside needs one: a replay, like an eager step, joins the side stream before its stream runs anything else."""
+    for e in _wcache.values():
+        if isinstance(e[3][-1], dict):
+            e[3][-1].pop("bwd_event", None)
+
+
+def reinstate_weights(snap):
+    """Make the entries of a weights_in() snapshot the caches' again, valid at the current epochs: for a caller that has just
+    recomputed every tensor they hold from the current weights (a replay of the graph that made them)."""
+    ents, blocks = snap
+    for k, V, g, val in ents:
+        _wcache[k] = (V, g, _token(V, g), val)
+        _wcache.move_to_end(k)
+    for k, e in blocks:
+        _block_cache[k] = e
+        _block_cache.move_to_end(k)
+    while len(_wcache) > _WCACHE_MAX:
+        _wcache.popitem(last=False)
+    while len(_block_cache) > 64:
+        _block_cache.popitem(last=False)
 
 
 # ------------------------------------------------------------------------------- raw launchers
@@ -789,11 +844,16 @@ def _wide_operands(per_layer, layers, row0, nrows, order, F, desc):
 def _split_block_weights(Vs, per_layer, plan, F):
     """Operands of a dense block computed as "wide convolutions of finished channel groups + short growth chains"
     (DenseBlockFunction): per wide convolution the gathered weights and their Winograd-domain filters, per layer the
-    rows of its own chain as contiguous tensors.  Cached for as long as the per-layer normalised weights are."""
+    rows of its own chain as contiguous tensors.  Cached for as long as the per-layer normalised weights are.  The operands
+    are functions of the weights and of the cut, not of the batch (the Winograd filters depend on the channel counts
+    alone, and which convolutions take the Winograd path does not depend on N): the entry is shared by every batch size
+    with the same cut -- the critic's blocks run on nb images in a generator step and on 2 nb in a critic step, and a
+    critic step reads the operands that the generator step before it made (trainer.GraphedSteps: the "gen1" graph's)."""
     key = id(Vs[0])
     ws = [pl[0] for pl in per_layer]
     hit = _block_cache.get(key)
-    if hit is not None and len(hit[0]) == len(ws) and all(a is b for a, b in zip(hit[0], ws)) and hit[2] == plan["key"]:
+    cut = plan["key"][1:]             # (N, ...): everything but the batch
+    if hit is not None and len(hit[0]) == len(ws) and all(a is b for a, b in zip(hit[0], ws)) and hit[2] == cut:
         _block_cache.move_to_end(key)
         return hit[1]
     L = len(per_layer)
@@ -844,7 +904,7 @@ def _split_block_weights(Vs, per_layer, plan, F):
                                                               ctypes.cast(pf, ctypes.c_void_p), n, _lib.stream_ptr()),
                        "dense16_prepare_filters")
             val["_h2_flat"] = flat_q
-    _block_cache[key] = (ws, val, plan["key"])
+    _block_cache[key] = (ws, val, cut)
     while len(_block_cache) > 64:
         _block_cache.popitem(last=False)
     return val

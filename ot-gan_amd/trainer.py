@@ -316,8 +316,9 @@ class OTGAN:
         finally:
             ops.SIDE_STREAM = None
         self._mark_step_end()
-        if kind == "disc":
-            self._d_weights_in_graph = False      # the critic changed: graphs that read its cached operands wait for a refresh
+        # the critic changed (critic step), or the host cache may now hold its operands as tensors of this eager step: graphs
+        # that read the "gen1" graph's wait until its next replay has reinstated them (GraphedSteps)
+        self._d_weights_in_graph = False
         self.step_counter += 1
         self.last = {"kind": kind, "distance": dist, "entropy": ent}      # device scalars, no sync
         if not apply_updates:
@@ -464,8 +465,9 @@ class OTGAN:
 
     def load_state_dict(self, sd):
         from . import ops
-        if self.graphs is not None:
-            self.graphs.drop("checkpoint loaded (the optimisers' moment buffers are new tensors)", recapture=True)
+        moments = lambda: [id(t) for o in (self.gen_optimizer, self.disc_optimizer) for st in getattr(o, "state", ())
+                           for t in st.values() if t is not None]
+        before = moments()
         with torch.no_grad():
             for t in (self.discriminator, self.generator):
                 for k, v in t.named_variables().items():
@@ -483,6 +485,13 @@ class OTGAN:
             self.disc_optimizer.load_state_dict(opt["disc"])
         ops.bump_weights_epoch()
         self.step_counter = int(sd.get("step_counter", 0))
+        if self.graphs is not None:
+            if moments() != before:
+                self.graphs.drop("checkpoint loaded (the optimisers' moment buffers are new tensors)", recapture=True)
+            else:
+                # every buffer a captured step reads was written in place: the graphs stay valid.  The critic's cached operands
+                # changed, so "gen" and "disc" wait for the next "gen1" replay, which recomputes them (GraphedSteps)
+                self._d_weights_in_graph = False
 
     def check_finite(self):
         """Synchronising sanity check of the last step's scalars (the persistent Sinkhorn kernel
@@ -500,9 +509,19 @@ class OTGAN:
             if b is not None:
                 b.remove()
         self.disc_buckets = self.gen_buckets = None
+        from . import ops
+        streams = [self._side_stream]
         if self.graphs is not None:
+            streams.append(self.graphs.stream)
             self.graphs.drop("trainer closed")
             self.graphs = None
+        # the module-level caches would keep this run's weight operands and workspaces alive after it
+        for t in (self.disc_params[0], self.gen_params[0], self.ema.average(self.gen_params[0])):
+            ops.forget_weights(t)
+        for s in streams:
+            if s is not None:
+                ops.forget_stream(s)
+                matching.forget_stream(s)
 
 
 class GraphedSteps:
@@ -517,10 +536,28 @@ class GraphedSteps:
         "gen"   every later generator step of the period: reads them.
     The first period always runs eagerly (workspaces, function attributes, optimiser state, device tables are created
     there); from then on a kind is captured the first time it is due -- which is the order gen1, gen, disc -- and
-    replayed afterwards.  What crosses graph boundaries: the critic's cached operands (written by "gen1", read by "gen"
-    and "disc": captured after it, so they hold its addresses) and the parameter / moment / EMA buffers (static).  The
-    generator's cached operands never cross: every kind recomputes them (it changed in the previous step; "gen1"
-    invalidates them itself, the critic step before it does not touch the generator).
+    replayed afterwards.
+
+    What crosses graph boundaries.  A capture does not record the host's weight caches (ops.cached_weights, the dense-block
+    operands, the Winograd filters made lazily for the input gradient): a lookup that HITS during the capture bakes the
+    address of an existing tensor into the graph, and that tensor must then hold the right values at every replay.  So:
+      * the parameter / moment / EMA buffers cross (static);
+      * the generator's cached operands, live and EMA, never cross: `_capture` invalidates them for every kind, so every
+        graph recomputes them from the current weights.  Anything else that ran between steps -- sample() at an epoch end,
+        an eager step -- may have left valid entries behind, and a graph that read them would keep reading a frozen
+        generator (and, once the entry is replaced, freed memory);
+      * the critic's cached operands are recomputed by "gen1" (its capture invalidates them) and read by "gen" and "disc",
+        which are captured only when the host cache holds exactly the "gen1" graph's tensors: right after a "gen1" replay.
+        The host entries outlive that moment only as long as their tokens do (the next critic step bumps them), so the
+        entries the "gen1" capture made are kept here and reinstated after every "gen1" replay (ops.weights_in /
+        reinstate_weights), and `_d_weights_in_graph` -- may "gen" / "disc" run now? -- is set by "gen1" / "gen" replays
+        only and cleared by every critic step and every eager step.  The critic's filters are therefore made once per
+        period, by "gen1", and not again by "gen" or "disc" (the round-6 replay speed-up; tests/test_step_graph_interleave_gpu.py
+        checks what every capture reads).
+    A checkpoint load writes the parameters, EMA shadows and optimiser moments in place (OTGAN.load_state_dict), so the
+    graphs stay; like an eager step it makes "gen" and "disc" wait for the next "gen1" replay.
+    The side-stream events a capture recorded are dropped when it ends (ops.forget_side_events): inside the graph they
+    became dependencies; outside it a replay orders everything it wrote before what its stream runs next.
 
     What changes from step to step comes from device memory: the data batch (copied into a static buffer), the RNG
     (torch's graph-safe generator state) and Adam's bias corrections (`coef_dev`, written before each replay with the
@@ -546,9 +583,11 @@ class GraphedSteps:
         self.stream = None
         self.warm = 0             # eager steps seen
         self.dead = None          # reason, once disabled
+        self.critic_ops = None    # the critic's cache entries the "gen1" capture made (ops.weights_in)
 
     def drop(self, why, recapture=False):
         self.graphs = {}
+        self.critic_ops = None
         self.m._d_weights_in_graph = False
         self.warm = 0
         if not recapture:
@@ -593,6 +632,8 @@ class GraphedSteps:
         m.step_counter += 1
         m._d_weights_in_graph = kind != "disc"
         self._bump_written(kind)
+        if kind == "gen1" and self.critic_ops is not None:
+            ops.reinstate_weights(self.critic_ops)       # the replay has just recomputed them: "gen" and "disc" read these
         return {"kind": "disc" if kind == "disc" else "gen", "distance": dist, "entropy": ent}
 
     def _bump_written(self, kind):
@@ -602,11 +643,16 @@ class GraphedSteps:
         is what lets "gen" and "disc" be captured reading them.  (Until round 6 this bumped the global epoch: every kind was
         then captured with the critic's cache invalid and recomputed the critic's normalised weights and Winograd filters
         in every replay -- more work than the eager step it was measured against)"""
-        from . import ops
         m = self.m
         ts = list(m.disc_params if kind == "disc" else m.gen_params)
         if kind != "disc":
             ts += [m.ema.average(p) for p in m.gen_params]
+        self._bump(ts)
+
+    @staticmethod
+    def _bump(ts):
+        """Invalidate the cached operands of the parameters `ts` (once per storage)."""
+        from . import ops
         seen = set()
         for t in ts:
             key = t.untyped_storage().data_ptr()
@@ -626,9 +672,12 @@ class GraphedSteps:
                 if opt.coef_dev is None:
                     opt.coef_dev = torch.ones(2, dtype=torch.float32, device=m.device)
         self.x.copy_(x_data)
+        # what this graph recomputes and what it reads (class comment): the generator's operands, live and EMA, are recomputed
+        # in every graph; the critic's in "gen1" ("gen" and "disc" run only while the host cache holds the "gen1" graph's)
+        ts = list(m.gen_params) + [m.ema.average(p) for p in m.gen_params]
         if kind == "gen1":
-            # the generator's cached operands must not cross graphs (see the class comment): recompute them here
-            ops.bump_weights_epoch(m.gen_params[0])
+            ts += list(m.disc_params)
+        self._bump(ts)
         saved_t = (m.gen_optimizer.t, m.disc_optimizer.t)
         ops.reset_amax_pool()
         g = torch.cuda.CUDAGraph()
@@ -639,13 +688,23 @@ class GraphedSteps:
             # parallel branches wherever the eager step runs two streams
             ops.SIDE_STREAM = m._side_stream if m.fork_wgrad else None
             with torch.cuda.graph(g, stream=self.stream):
-                dist, ent, _ = m._step_body(self.x, "disc" if kind == "disc" else "gen")
+                try:
+                    dist, ent, _ = m._step_body(self.x, "disc" if kind == "disc" else "gen")
+                except BaseException:
+                    # join the second stream before the capture ends: a fork left open fails the end of the capture and
+                    # leaves the stream capturing, which breaks every later launch of the process and hides this error
+                    if ops.SIDE_STREAM is not None:
+                        torch.cuda.current_stream().wait_stream(ops.SIDE_STREAM)
+                    raise
         finally:
             ops.SIDE_STREAM = None
             m.gen_optimizer.capturing = m.disc_optimizer.capturing = False
             m.gen_optimizer.t, m.disc_optimizer.t = saved_t      # (the capture only recorded the launches)
             ops.reset_amax_pool()                                 # eager code must not draw from the graph's pool
+            ops.forget_side_events()
         self.graphs[kind] = (g, dist, ent)
+        if kind == "gen1":
+            self.critic_ops = ops.weights_in(m.disc_params[0])
 
 
 def rank_log_kernel_slices(rank, world, f_gen, f_dat, fa, fb, lam):

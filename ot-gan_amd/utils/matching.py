@@ -44,6 +44,12 @@ def _workspace(nbytes, device):
     return buf
 
 
+def forget_stream(stream):
+    """Drop the scratch buffer of a stream that is no longer used."""
+    for key in [k for k in _ws_cache if k[1] == stream.cuda_stream]:
+        del _ws_cache[key]
+
+
 def _check_lists(features_a, features_b):
     if len(features_a) != len(features_b) or len(features_a) == 0:
         raise ValueError("features_a and features_b must be non-empty lists of equal length")

@@ -15,6 +15,7 @@ nn.py:133-162 are built but never run by train.py, so V ~ N(0, 0.05), g = 1, b =
 import contextlib
 import os
 import threading
+import weakref
 from collections import OrderedDict
 
 import torch
@@ -95,7 +96,7 @@ class FlatGroup:
     per tensor (DenseNet has ~300 tensors per network).  Tensors whose size is not a multiple of
     four floats (the RGB layer's g and b) go last so that every other view stays 16-byte aligned."""
 
-    _by_param = {}
+    _by_param = weakref.WeakValueDictionary()   # id(member) -> group, while the group lives (its optimiser / EMA hold it)
 
     def __init__(self, params):
         order = [p for p in params if p.numel() % 4 == 0] + [p for p in params if p.numel() % 4 != 0]
@@ -451,9 +452,14 @@ class _Updates:
         if len(sd["slots"]) != len(self.state):
             raise ValueError("optimiser state does not match this parameter layout")
         for st, saved, p in zip(self.state, sd["slots"], targets):
-            st.clear()
+            for k in [k for k in st if k not in saved]:
+                del st[k]
             for k, v in saved.items():
-                st[k] = None if v is None else v.to(p.device).clone()
+                cur = st.get(k)
+                if v is not None and cur is not None and cur.shape == v.shape and cur.dtype == v.dtype:
+                    cur.copy_(v)      # in place: a captured step (trainer.GraphedSteps) keeps reading this buffer
+                else:
+                    st[k] = None if v is None else v.to(p.device).clone()
 
 
     def _step_gather(self, grads, lr):
