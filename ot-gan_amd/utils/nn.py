@@ -183,6 +183,15 @@ class Template:
         return OrderedDict(self.store.vars)
 
     def reset(self, seed=1, device=None):
+        # the variables that go away can never hit the weight cache again (it is keyed by the variable object and holds it):
+        # without this, every run that was not closed keeps its normalised weights and Winograd filters -- gigabytes for a
+        # DCGAN -- until 1024 newer entries evict them
+        seen = set()
+        for v in self.store.vars.values():
+            key = v.untyped_storage().data_ptr()
+            if key not in seen:
+                seen.add(key)
+                ops.forget_weights(v)
         self.store = VariableStore(self.name, device=device, seed=seed)
 
     def flatten(self):
