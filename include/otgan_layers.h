@@ -450,4 +450,15 @@ int otgan_incep_resize_f32(int N, int H, int W, int C, int OH, int OW, int align
 int otgan_incep_head_f32(int N, int HW, int C, int ldx, int classes, const float* x, const float* w, float* pool3,
                          float* logits, float* probs, void* stream);
 
+/*
+ * Feature moments of the Frechet Inception Distance (utils/fid.py), fp64 MFMA, in place:
+ *   sum[i] += sum_k x[k][i],  outer[i][j] += sum_k x[k][i] * x[k][j]   for the n rows of x.
+ * x: fp32 [n][C] with row stride ldx >= C (pool3 of otgan_incep_head_f32, or a column slice of a wider buffer); sum [C]
+ * and outer [C][C] fp64.  Any n >= 0 (n == 0 is a no-op), any C % 4 == 0.  The fp32 inputs are converted to fp64 before
+ * the multiply, so every product is exact and only the summation over the rows rounds.  Only elements on or above the
+ * diagonal of outer are read; each is computed once and stored to [i][j] and [j][i], so outer is exactly symmetric.
+ * Deterministic: the same sequence of calls gives the same bits (no atomics, fixed row order).  No workspace.
+ */
+int otgan_moments_update_f64(int n, int C, int ldx, const float* x, double* sum, double* outer, void* stream);
+
 #endif /* OTGAN_LAYERS_H */

@@ -121,4 +121,5 @@ SIGNATURES = {
     "otgan_incep_pool_f32": (c_int, [ctypes.POINTER(IncepPoolDesc), c_fp, c_fp, c_fp]),
     "otgan_incep_resize_f32": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_float, c_fp, c_fp, c_fp]),
     "otgan_incep_head_f32": (c_int, [c_int, c_int, c_int, c_int, c_int, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp]),
+    "otgan_moments_update_f64": (c_int, [c_int, c_int, c_int, c_fp, c_fp, c_fp, c_fp]),
 }

@@ -11,7 +11,8 @@ physical GPUs (= torch.distributed world size): every rank owns nr_gpu / world s
 Added flags (not in the reference): --synthetic (random CIFAR-shaped data instead of the
 pickled dataset), --synthetic_size, --matching_scope global|local, --max_steps, --image_size, --save_every,
 --data_dependent_init, --eval_every / --eval_samples / --inception_model (the reference's Inception-score hook,
-train.py:245-272: --inception_model takes the reference's own 2015 graph file, or a TorchScript classifier).
+train.py:245-272: --inception_model takes the reference's own 2015 graph file, or a TorchScript classifier),
+--fid_stats / --fid_real_samples (the Frechet Inception Distance beside every score, utils/fid.py).
 
 Checkpoints (`<save_dir>/med_gan_params-<epoch>`, the reference's naming, train.py:275-277) are torch pickles
 of {variable name: tensor} plus optimiser moments / step count and EMA shadows (which the reference's
@@ -67,6 +68,13 @@ def build_parser():
                    help="the reference's 2015 Inception graph (classify_image_graph_def.pb, inception-2015-12-05.tgz or the "
                         'directory holding the .pb; runs on the GPU kernels) or a TorchScript classifier (float32 images '
                         '[n,H,W,3] in 0..255 -> class probabilities); without it the Inception-score hook is skipped')
+    p.add_argument('--fid_stats', type=str, default='',
+                   help="report the Frechet Inception Distance beside every Inception score, against the pool_3 statistics in "
+                        "this .npz (keys mu, sigma: the circulated fid_stats_*.npz files load as they are); a missing file is "
+                        "computed from the training set before the first step and saved there.  Needs the 2015 graph as "
+                        "--inception_model.  '' = off")
+    p.add_argument('--fid_real_samples', type=int, default=0,
+                   help='training images behind a computed --fid_stats file: the first N (0 = all)')
     p.add_argument('--step_graph', type=int, nargs='?', const=1, default=None, choices=(0, 1),
                    help='replay whole steps as hipGraphs after the first period (single-process runs; bit-identical to the '
                         'eager steps).  Default: on for --model densenet (launch-bound: replay 25.5 ms against 27.6 - 29.6 ms), '
@@ -78,17 +86,35 @@ def inception_hook(model, args, classifier, state, rank=0, world=1):
     """train.py:245-272: scores of `eval_samples` samples of the generator and of its EMA copy, running maximum.
     Every rank takes part: it draws and classifies its share of the samples (its own latent stream, seed + rank) and
     the class probabilities are gathered, so no rank waits at the next epoch's first collective while rank 0 alone
-    samples and scores 2 x 50 000 images.  All ranks get the same scores; rank 0 prints them."""
+    samples and scores 2 x 50 000 images.  All ranks get the same scores; rank 0 prints them.
+
+    With the real data's pool_3 statistics in `state["fid_real"]` = (mu, sigma) (--fid_stats; device classifier only) the
+    same forward pass also feeds the Frechet Inception Distance (utils/fid.py): pool_3 of exactly the `eval_samples`
+    samples the score covers goes into fp64 moments on the device, one SUM all-reduce per evaluated model replaces a
+    feature gather, rank 0 finalises on the host and broadcasts the scalar."""
     from .utils.inception import class_probabilities, inception_score_from_probs
     from . import parallel
     on_device = hasattr(classifier, "probs_from_generator")    # utils.inception_net.InceptionNet: samples stay on the GPU
+    fid_real = state.get("fid_real") if on_device else None
     share = -(-args.eval_samples // world)
+    # the gather below is cut to eval_samples rows: of this rank's share the first `mine` survive
+    mine = min(max(args.eval_samples - rank * share, 0), share)
     out = {}
+    if fid_real is not None:
+        from .utils import fid
+        state.setdefault("fid_min", float("inf"))
+        state.setdefault("fid_iter", 0)
     for tag, ema in (("", False), ("EMA ", True)):
         probs, have = [], 0
+        if fid_real is not None:
+            acc = fid.MomentAccumulator(classifier.plan.pool3_channels, classifier.device)
         while have < share:
             x = model.sample(min(1000, share - have), ema=ema)
-            if on_device:
+            if fid_real is not None:
+                p, pool3 = classifier.probs_and_pool3_from_generator(x.float())
+                probs.append(p)
+                acc.update(pool3[:min(max(mine - have, 0), x.shape[0])])
+            elif on_device:
                 probs.append(classifier.probs_from_generator(x.float()))                      # 127.5 (x + 1) folded in
             else:
                 x = x.float().cpu().numpy()
@@ -105,9 +131,46 @@ def inception_hook(model, args, classifier, state, rank=0, world=1):
         if score[0] > state["max"]:
             state["max"], state["iter"] = score[0], state["epoch"]
         out[tag.strip() or "live"] = score
+        if fid_real is not None:
+            acc.all_reduce()
+            d = torch.zeros(1, dtype=torch.float64, device=classifier.device)
+            if rank == 0:
+                d[0] = fid.frechet_distance(*fid.stats_from_moments(*acc.moments()), fid_real[0], fid_real[1])
+                print('%sFID was %.4f' % (tag, float(d)))
+            d = float(parallel.broadcast_(d))
+            if d < state.get("fid_min", float("inf")):
+                state["fid_min"], state["fid_iter"] = d, state["epoch"]
+            out["fid_" + (tag.strip() or "live")] = d
     if rank == 0:
         print('max inception score was %.6f, iter was %d' % (state["max"], state["iter"]))
+        if fid_real is not None:
+            print('min FID was %.4f, iter was %d' % (state["fid_min"], state["fid_iter"]))
     return out
+
+
+def real_fid_stats(args, classifier, trainx, rank=0, world=1):
+    """--fid_stats: (mu, sigma) of the real data's pool_3, loaded from the file or -- when rank 0 does not find it --
+    computed by all ranks from the first --fid_real_samples training images and saved by rank 0.  None (said once) when
+    the classifier is not the device network of the 2015 graph: FID is defined on its pool_3."""
+    from . import parallel
+    from .utils import fid
+    if not hasattr(classifier, "probs_and_pool3_from_generator"):
+        if rank == 0:
+            print('--fid_stats: FID needs the 2015 Inception graph as --inception_model (it is defined on its pool_3); skipped')
+        return None
+    C = classifier.plan.pool3_channels
+    there = torch.tensor([1.0 if os.path.exists(args.fid_stats) else 0.0], device=classifier.device)
+    if float(parallel.broadcast_(there)):          # rank 0 decides: every rank takes the same branch
+        mu, sigma, n = fid.load_stats(args.fid_stats, C)
+        if rank == 0:
+            print('FID statistics of the real data: loaded %s (%s)' % (args.fid_stats, '%d images' % n if n else 'n not recorded'))
+        return mu, sigma
+    x = trainx[:args.fid_real_samples] if args.fid_real_samples else trainx
+    mu, sigma, n = fid.dataset_stats(classifier, x, rank, world)
+    if rank == 0:
+        fid.save_stats(args.fid_stats, mu, sigma, n)
+        print('FID statistics of the real data: computed from %d training images, saved to %s' % (n, args.fid_stats))
+    return mu, sigma
 
 
 def load_cifar(data_dir, subset='train'):
@@ -210,6 +273,8 @@ def main(argv=None, self_launch=False):
         classifier = load_classifier(args.inception_model, dev)
     elif rank == 0:
         print('no --inception_model: the Inception-score hook (reference train.py:245-272) is skipped')
+    if args.fid_stats:
+        score_state["fid_real"] = real_fid_stats(args, classifier, trainx, rank, world)
     start_time = time.time()
     total = 0
     for epoch in range(current_epoch, 1000000):

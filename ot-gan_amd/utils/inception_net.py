@@ -426,6 +426,12 @@ class InceptionNet:
         """class probabilities of generator output x in [-1, 1]: the images 127.5 (x + 1)"""
         return self.run(x, 127.5, 127.5)[2]
 
+    def probs_and_pool3_from_generator(self, x):
+        """(class probabilities, pool_3) of generator output x in [-1, 1] from ONE forward pass: the Inception score
+        reads the first, the Frechet distance (utils/fid.py) the second"""
+        pool3, _, probs = self.run(x, 127.5, 127.5)
+        return probs, pool3
+
     def __call__(self, images):
         """numpy [n, H, W, 3] in 0..255 -> numpy probabilities: the classifier callable of utils/inception.py"""
         import torch

@@ -1,12 +1,14 @@
 """Throughput of the Inception evaluation network (utils/inception_net.py, csrc/inception.hip) on one GPU.
 
-    python tools/bench_inception.py [--graph classify_image_graph_def.pb | .tgz | dir] [--batch 500]
+    python tools/bench_inception.py [--graph classify_image_graph_def.pb | .tgz | dir] [--batch 500] [--moments]
 
 Without --graph it synthesizes the full 2015 topology with random weights (tests/inception_graphs.py: same layers,
 same FLOP count).  Input: generator-like 32 x 32 images in [-1, 1] through probs_from_generator (the training hook's
 path: resize to 299 x 299 and the affines in one kernel).  Prints img/s and TFLOP/s at the batch size, from the plan's
 FLOP count and HIP-event timing after warm-up, and the projected time of one evaluation of the reference
-(2 x 50 000 samples, train.py:245-272), as one JSON line.
+(2 x 50 000 samples, train.py:245-272), as one JSON line.  --moments: also the time of one fp64 moment update of the
+batch's pool_3 (utils/fid.py, csrc/moments.hip; HIP events, same run) beside the forward pass, and the wall time of the
+host finalisation of one Frechet distance at that width (two eigh).
 """
 import argparse
 import json
@@ -26,6 +28,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--iters", type=int, default=5)
     ap.add_argument("--image_size", type=int, default=32)
+    ap.add_argument("--moments", action="store_true", help="time the FID moment update of the batch's pool_3 as well")
     a = ap.parse_args()
     import torch
     from otgan_amd.utils import inception_net, tfgraph
@@ -56,6 +59,29 @@ def main():
            "eval_2x50000_s": round(100000 / img_s, 2), "convs": len(plan.convs()),
            "arena_gb": round(plan.arena_floats_per_image * 4 * a.batch / 1e9, 2), "lower_s": round(t_load, 2),
            "graph": a.graph or "synthesized full 2015 topology", "probs_finite": bool(torch.isfinite(p).all())}
+    if a.moments:
+        from otgan_amd.utils import fid
+        C = plan.pool3_channels
+        pool3 = net.run(x, 127.5, 127.5)[0]
+        acc = fid.MomentAccumulator(C, dev)
+        for _ in range(a.warmup):
+            acc.update(pool3)
+        torch.cuda.synchronize()
+        reps = 20 * a.iters                                     # a short kernel: a longer window than the forward pass's
+        e0.record()
+        for _ in range(reps):
+            acc.update(pool3)
+        e1.record()
+        torch.cuda.synchronize()
+        mms = e0.elapsed_time(e1) / reps
+        other = fid.MomentAccumulator(C, dev).update(net.run(x.flip(0).neg(), 127.5, 127.5)[0])
+        ma, mb = acc.moments(), other.moments()
+        t0 = time.time()
+        d = fid.frechet_distance(*fid.stats_from_moments(*ma), *fid.stats_from_moments(*mb))
+        out.update({"moments_ms_per_batch": round(mms, 4), "moments_share_of_forward": round(mms / ms, 5),
+                    "moments_fp64_tflops": round(2.0 * a.batch * C * C / (mms * 1e-3) / 1e12, 2), "pool3_channels": C,
+                    "allreduce_mb": round(8 * (C * C + C + 1) / 1e6, 1), "feature_gather_mb_50000": round(4 * 50000 * C / 1e6, 1),
+                    "fid_finalise_s": round(time.time() - t0, 2), "fid_finite": bool(d == d and abs(d) != float("inf"))})
     print(json.dumps(out))
 
 
