@@ -1949,14 +1949,25 @@ struct MatchWs {
   long planeF, planeP;
   size_t bytes;
 };
+// K splits that size the partial sums of a cost stage: whichever engine runs, its planner's count fits
+inline int cost_partial_splits(int P, int n, int m, int D, bool x3) {
+  const int fp32 = plan_cost(P, n, m, D).nsplit, split = x3 ? x3_plan_cost(P, n, m, D).nsplit : 0;
+  return fp32 > split ? fp32 : split;
+}
+// the one "workspace too small" failure of every entry point that takes a workspace
+int check_workspace(const void* workspace, size_t got, size_t need) {
+  if (!workspace || got < need) {
+    otgan_set_error("workspace too small: need %zu bytes, got %zu", need, got);
+    return OTGAN_ERR_WORKSPACE;
+  }
+  return OTGAN_OK;
+}
 MatchWs carve_match(void* base, size_t cap, int P, int n, int D, int feat_rows, bool grad = false) {
   Carver c(base, cap);
   MatchWs w;
-  const CostPlan cp = plan_cost(P, n, n, D);
   const size_t pnm = (size_t)P * n * n;
   w.x3 = x3_shape_ok(n, n, D);
-  int nsplit = cp.nsplit;
-  if (w.x3 && x3_plan_cost(P, n, n, D).nsplit > nsplit) nsplit = x3_plan_cost(P, n, n, D).nsplit;
+  const int nsplit = cost_partial_splits(P, n, n, D, w.x3);
   w.sq_a = (float*)c.take(sizeof(float) * feat_rows);
   w.sq_b = (float*)c.take(sizeof(float) * feat_rows);
   // grad variant (otgan_matching_two_batch_grad_f32): feature stack [a1 b1 b2 a2 a1 b1] (3 n-row blocks more than the
@@ -2009,6 +2020,220 @@ void x3_split_plans(const MatchWs& w, const float* plan, const float* planT, int
   x3_split_group(jobs, 2, x3_hdr(w.PT), e0, s);
 }
 
+// ---------------------------------------------------------------------------------------
+// the matching entry points' shared description (feature blocks, problems, stack layouts, feature source) and the
+// stages all of them run: begin (checks, workspace), solve (log-kernels, Sinkhorn), finish (entropy, distance, statistics)
+// ---------------------------------------------------------------------------------------
+// Feature blocks of n rows.  Two-batch: fa = [a1; a2], fb = [b1; b2] (utils/matching.py:16-19); single-batch: fa = a, fb = b.
+// Block b is part b % 2 of array b / 2.
+enum FeatBlock { A1 = 0, A2 = 1, B1 = 2, B2 = 3, SA = A1, SB = B1 };
+
+// problem p of a matching call: the cost and plan of block x[p] against block y[p], diag[p] added on the diagonal
+struct ProblemSet {
+  int P, nfeat;     // problems, feature blocks they read
+  int x[kMaxProb], y[kMaxProb];
+  bool has_diag;
+  float diag[kMaxProb];
+  const float* diag_or_null() const { return has_diag ? diag : nullptr; }
+};
+// problem order of the reference (matching.py:41-43): a1a2, b2b1, a1b1, a1b2, a2b1, a2b2
+const ProblemSet kTwoBatch = {6, 4, {A1, B2, A1, A1, A2, A2}, {A2, B1, B1, B2, B1, B2}, false, {}};
+// matching.py:99-110: aa, bb (999 on the diagonal: no sample is matched with itself), ab
+const ProblemSet kSingleBatch = {3, 2, {SA, SB, SA}, {SA, SB, SB}, true, {999.f, 999.f, 0.f}};
+
+// a stacked fp16 feature operand: the feature blocks in the order it holds them, n rows each
+struct StackLayout {
+  int nblocks;
+  int block[6];
+  long row(int b, int n) const {      // first row of (the first copy of) feature block b
+    int i = 0;
+    while (i < nblocks - 1 && block[i] != b) ++i;
+    return (long)i * n;
+  }
+  StackLayout first(int k) const { StackLayout l = *this; l.nblocks = k; return l; }
+};
+// [fa; fb], what x3_split_features writes: the inference entry points and the single-batch pair
+const StackLayout kStackArrays = {4, {A1, A2, B1, B2}};
+const StackLayout kStackSingle = {2, {SA, SB}};
+// training-mode two-batch matching: every difference contracts over three ADJACENT blocks (matching_grad_impl); generator
+// steps read the first four.  Also the layout of the caller's stack: otgan_matching_stack_split_f32, FeatureStack.rank_plan
+const StackLayout kStackGrad = {6, {A1, B1, B2, A2, A1, B1}};
+
+// Where a call's features come from: two fp32 arrays and their pitch, or a stack the caller split already
+// (otgan_matching_stack_split_f32).  A stack has no fp32 blocks: only the split-precision engine reads it.
+struct FeatSrc {
+  const float *fa, *fb;
+  long ld;
+  const void* stack;
+  static FeatSrc arrays(const float* fa, const float* fb, long ld) { return FeatSrc{fa, fb, ld, nullptr}; }
+  static FeatSrc presplit(const void* stack) { return FeatSrc{nullptr, nullptr, 0, stack}; }
+  bool given() const { return stack || (fa && fb); }
+  bool pitch_ok(int D) const { return stack || ld >= D; }
+  // what the split-precision engine's loaders ask of the source
+  bool engine_ok() const { return stack ? aligned16(stack) : ld % 4 == 0 && aligned16(fa) && aligned16(fb); }
+  const float* block(int b, int n) const { return stack ? nullptr : (b / 2 ? fb : fa) + (long)(b % 2) * n * ld; }
+};
+
+// one matching call from begin to finish
+struct MatchCall {
+  const ProblemSet& set;
+  int n, D;
+  float lambda;
+  int iters;
+  hipStream_t s;
+  MatchWs w;
+};
+
+// Begin: the checks every entry point makes (the entry points put their own between these, in their order) ...
+int match_check_sizes(const char* rows_name, int n, int D, const FeatSrc& f, long ldo, int iters) {
+  OTGAN_CHECK_ARG(n > 0 && D > 0 && f.pitch_ok(D) && ldo >= D && iters >= 0, "bad sizes %s=%d D=%d", rows_name, n, D);
+  return OTGAN_OK;
+}
+// (a rank's rows: inside [0, total) and, where the rows are two mini-batches of N > 0, inside one of them)
+int match_check_rows(int row_begin, int row_count, int total, int N) {
+  OTGAN_CHECK_ARG(row_begin >= 0 && row_count > 0 && row_begin + row_count <= total,
+                  "row range [%d, %d) outside [0, %d)", row_begin, row_begin + row_count, total);
+  OTGAN_CHECK_ARG(!N || (row_begin + row_count - 1) / N == row_begin / N, "row range must not straddle the two mini-batches");
+  return OTGAN_OK;
+}
+// ... and the workspace
+int match_begin(MatchCall& c, bool grad, void* workspace, size_t workspace_bytes) {
+  c.w = carve_match(workspace, workspace_bytes, c.set.P, c.n, c.D, c.set.nfeat / 2 * c.n, grad);
+  return check_workspace(workspace, workspace_bytes, c.w.bytes);
+}
+
+// Solve: the log-kernels -- K_pre, or the cost stage on the engine the caller chose -- then the Sinkhorn plans and their
+// statistics.  x3: the features lie split in c.w.FP in layout `lay`, or split_in_scope puts them there (the two inference
+// entry points count their split into the cost class that bench.py reports, the others split before they call).  Else the
+// fp32 engine reads the blocks of f; sq: the toy cost's row statistics per feature block.
+template <class Split>
+int match_solve(const MatchCall& c, bool x3, const StackLayout& lay, const FeatSrc& f, int cost_kind, const float* const* sq,
+                const float* K_pre, Split&& split_in_scope) {
+  const ProblemSet& ps = c.set;
+  const MatchWs& w = c.w;
+  const int n = c.n, D = c.D;
+  const float* K = K_pre;
+  if (!K_pre) {
+    int rc;
+    if (x3) {
+      long xrow[kMaxProb], yrow[kMaxProb];
+      for (int p = 0; p < ps.P; ++p) { xrow[p] = lay.row(ps.x[p], n); yrow[p] = lay.row(ps.y[p], n); }
+      ProfScope scope(OTGAN_PROF_COST_GEMM, 2.0 * ps.P * n * (double)n * D, 4.0 * ps.nfeat * n * (double)D, c.s);
+      split_in_scope();
+      rc = launch_cost_x3(w.FP, w.planeF, (long)lay.nblocks * n, xrow, yrow, ps.diag_or_null(), ps.P, n, n, D, c.lambda,
+                          w.partial, w.K, c.s);
+    } else {
+      const float *X[kMaxProb], *Y[kMaxProb], *xsq[kMaxProb], *ysq[kMaxProb];
+      for (int p = 0; p < ps.P; ++p) {
+        X[p] = f.block(ps.x[p], n); Y[p] = f.block(ps.y[p], n);
+        xsq[p] = sq ? sq[ps.x[p]] : nullptr; ysq[p] = sq ? sq[ps.y[p]] : nullptr;
+      }
+      rc = launch_cost(X, Y, sq ? xsq : nullptr, sq ? ysq : nullptr, ps.diag_or_null(), ps.P, n, n, D, f.ld, c.lambda, cost_kind,
+                       w.partial, w.K, c.s);
+    }
+    if (rc) return rc;
+    K = w.K;
+  }
+  return launch_sinkhorn(K, ps.P, n, n, c.iters, c.lambda, w.plan, w.planT, w.stats, w.fg, c.s);
+}
+int match_solve(const MatchCall& c, bool x3, const StackLayout& lay, const FeatSrc& f, const float* K_pre) {
+  return match_solve(c, x3, lay, f, OTGAN_COST_COSINE, nullptr, K_pre, [] {});
+}
+
+// Finish: the entropy, the caller's form of the distance, the statistics where asked for
+template <class Distance>
+int match_finish(const MatchCall& c, float* entropy, double* stats, Distance&& distance) {
+  hipLaunchKernelGGL(entropy_finalize_kernel, dim3(1), dim3(1), 0, c.s, c.w.stats, c.set.P, c.n, entropy);
+  const int rc = distance();
+  if (rc) return rc;
+  if (stats) hipMemcpyAsync(stats, c.w.stats, sizeof(double) * 4 * c.set.P, hipMemcpyDeviceToDevice, c.s);
+  return OTGAN_OK;
+}
+// calc_distance's pass over the features and three of the matched arrays (the two inference entry points) ...
+int distance_dot3(const MatchCall& c, const FeatSrc& f, const float* f_aa, const float* f_bb, const float* f_ab, double denom,
+                  double* dist) {
+  return launch_distance(f.fa, f.fb, f_aa, f_bb, f_ab, (long)(c.set.nfeat / 2) * c.n * c.D, denom, dist, c.w.dot3, c.s, c.w.stats,
+                         c.set.P);
+}
+// ... or its closed form from the statistics of the six two-batch problems (every other two-batch entry point)
+int distance_closed_two_batch(const MatchCall& c, double* dist) {
+  hipLaunchKernelGGL(closed_form_distance_kernel, dim3(1), dim3(1), 0, c.s, c.w.stats, c.n, dist);
+  OTGAN_CHECK_LAUNCH("matching finalize");
+  return OTGAN_OK;
+}
+
+// The matched-feature arrays of the inference entry points.  A block: rows of out[which] (its second half of N rows
+// where half == 1) <- alpha * the sum of one or two plan . feature products, a term the plan of problem p or its transpose
+// times feature block feat.
+enum MatchedOut { F_AA, F_BB, F_AB, F_BA };
+struct MatchedBlock {
+  int out, half, nterms;
+  struct { int p; bool transposed; int feat; } t[2];
+  float alpha;
+};
+struct MatchedTable {
+  const MatchedBlock* blk;
+  int nblocks;
+  // split-precision engine: the transposed plans lie in problem order (operand PT), the plans in this order (operand PM),
+  // so that the two terms of a block are adjacent in their operand as their feature blocks are in kStackArrays
+  int orderM[kMaxProb];
+};
+// matching.py:64-83: eight [N, D] blocks, block 2 k + h = half h of array k
+const MatchedBlock kMatchedBlocksTwoBatch[8] = {
+    {F_AA, 0, 1, {{0, false, A2}}, 1.f},                    // a1 <- M_a1a2 . a2                    (:64)
+    {F_AA, 1, 1, {{0, true, A1}}, 1.f},                     // a2 <- M_a1a2^T . a1                  (:70)
+    {F_BB, 0, 1, {{1, true, B2}}, 1.f},                     // b1 <- M_b2b1^T . b2                  (:65)
+    {F_BB, 1, 1, {{1, false, B1}}, 1.f},                    // b2 <- M_b2b1 . b1                    (:71)
+    {F_AB, 0, 2, {{2, false, B1}, {3, false, B2}}, 0.5f},   // a1 <- (M_a1b1.b1 + M_a1b2.b2)/2      (:66,67,80)
+    {F_AB, 1, 2, {{4, false, B1}, {5, false, B2}}, 0.5f},   // a2 <- (M_a2b1.b1 + M_a2b2.b2)/2      (:68,69,80)
+    {F_BA, 0, 2, {{2, true, A1}, {4, true, A2}}, 0.5f},     // b1 <- (M_a1b1^T.a1 + M_a2b1^T.a2)/2  (:72,74,82)
+    {F_BA, 1, 2, {{3, true, A1}, {5, true, A2}}, 0.5f},     // b2 <- (M_a1b2^T.a1 + M_a2b2^T.a2)/2  (:73,75,82)
+};
+const MatchedTable kMatchedTwoBatch = {kMatchedBlocksTwoBatch, 8, {0, 1, 2, 4, 3, 5}};
+// matching.py:131-134
+const MatchedBlock kMatchedBlocksSingle[4] = {
+    {F_AA, 0, 1, {{0, false, SA}}, 1.f},   // M_aa . a
+    {F_BB, 0, 1, {{1, false, SB}}, 1.f},   // M_bb . b
+    {F_AB, 0, 1, {{2, false, SB}}, 1.f},   // M_ab . b
+    {F_BA, 0, 1, {{2, true, SA}}, 1.f},    // M_ab^T . a
+};
+const MatchedTable kMatchedSingle = {kMatchedBlocksSingle, 4, {0, 1, 2}};
+
+// rows [r0, r0 + cnt) of the blocks first, first + step, ... (nblk of them) of tab in one launch: a full call takes all of
+// them, a rank's call the four blocks of its half
+int apply_matched(const MatchCall& c, bool x3, const MatchedTable& tab, const StackLayout& lay, const FeatSrc& f, int first, int step,
+                  int nblk, float* const* out, long ldo, long half_stride, int r0, int cnt) {
+  const MatchWs& w = c.w;
+  const int n = c.n;
+  const size_t nn = (size_t)n * n;
+  auto outp = [&](const MatchedBlock& b) { return out[b.out] + b.half * half_stride; };
+  if (!x3) {
+    ApplyBlock blk[8];
+    memset(blk, 0, sizeof(blk));
+    for (int z = 0; z < nblk; ++z) {
+      const MatchedBlock& b = tab.blk[first + z * step];
+      blk[z].out = outp(b); blk[z].rows = cnt; blk[z].nterms = b.nterms; blk[z].alpha = b.alpha;
+      for (int t = 0; t < b.nterms; ++t)
+        blk[z].t[t] = ApplyTerm{(b.t[t].transposed ? w.planT : w.plan) + b.t[t].p * nn + (long)r0 * n, f.block(b.t[t].feat, n), (long)n, n};
+    }
+    return launch_apply(blk, nblk, cnt, c.D, f.ld, ldo, c.s);
+  }
+  float alpha[kMaxProb];     // a plan enters its operand with the weight of the block that reads it
+  int posM[kMaxProb];
+  for (int i = 0; i < c.set.P; ++i) posM[tab.orderM[i]] = i;
+  for (int i = 0; i < tab.nblocks; ++i)
+    for (int t = 0; t < tab.blk[i].nterms; ++t) alpha[tab.blk[i].t[t].p] = tab.blk[i].alpha;
+  x3_split_plans(w, w.plan, w.planT, c.set.P, n, tab.orderM, alpha, c.s);
+  X3ApplyBlock xb[8];
+  for (int z = 0; z < nblk; ++z) {
+    const MatchedBlock& b = tab.blk[first + z * step];
+    const bool tr = b.t[0].transposed;
+    xb[z] = X3ApplyBlock{tr ? w.PM : w.PT, (long)(tr ? posM[b.t[0].p] : b.t[0].p) * n, lay.row(b.t[0].feat, n), b.nterms * n, outp(b)};
+  }
+  // (PT is carved first: the base both operands' offsets are taken from)
+  return launch_apply_x3(xb, nblk, w.PT, x3_hdr(w.PT), w.planeP, n, w.FP, w.planeF, r0, cnt, c.D, ldo, c.s);
+}
+
 }  // namespace
 
 // =======================================================================================
@@ -2027,106 +2252,35 @@ int otgan_matching_two_batch_f32(const float* fa, const float* fb, int N, int D,
                                  float* f_bb, float* f_ab, float* f_ba, long ldo,
                                  float* entropy, double* dist, double* stats, void* workspace,
                                  size_t workspace_bytes, void* stream) {
+  const FeatSrc f = FeatSrc::arrays(fa, fb, ldf);
   OTGAN_CHECK_ARG(fa && fb && f_aa && f_bb && f_ab && f_ba && entropy && dist, "null pointer");
-  OTGAN_CHECK_ARG(N > 0 && D > 0 && ldf >= D && ldo >= D && iters >= 0, "bad sizes N=%d D=%d", N, D);
+  int rc = match_check_sizes("N", N, D, f, ldo, iters);
+  if (rc) return rc;
   OTGAN_CHECK_ARG(cost_kind == OTGAN_COST_COSINE || cost_kind == OTGAN_COST_SQEUCLID_MEAN,
                   "unknown cost kind %d", cost_kind);
   // the distance reduction walks the [2N, D] arrays linearly
   OTGAN_CHECK_ARG(ldf == D && ldo == D, "feature arrays must be contiguous (ld == D)");
-  hipStream_t s = (hipStream_t)stream;
-  MatchWs w = carve_match(workspace, workspace_bytes, 6, N, D, 2 * N);
-  if (!workspace || workspace_bytes < w.bytes) {
-    otgan_set_error("workspace too small: need %zu bytes, got %zu", w.bytes, workspace_bytes);
-    return OTGAN_ERR_WORKSPACE;
+  MatchCall c = {kTwoBatch, N, D, lambda, iters, (hipStream_t)stream};
+  if ((rc = match_begin(c, false, workspace, workspace_bytes))) return rc;
+  const bool toy = cost_kind == OTGAN_COST_SQEUCLID_MEAN;
+  const float* sq[4] = {c.w.sq_a, c.w.sq_a + N, c.w.sq_b, c.w.sq_b + N};   // per feature block
+  if (toy) {
+    hipLaunchKernelGGL(row_halfmeansq_kernel, dim3(ceil_div(2 * N, 4)), dim3(256), 0, c.s, fa, ldf,
+                       2 * N, D, c.w.sq_a);
+    hipLaunchKernelGGL(row_halfmeansq_kernel, dim3(ceil_div(2 * N, 4)), dim3(256), 0, c.s, fb, ldf,
+                       2 * N, D, c.w.sq_b);
   }
-  const float *fa1 = fa, *fa2 = fa + (long)N * ldf, *fb1 = fb, *fb2 = fb + (long)N * ldf;
-  // problem order of the reference (matching.py:41-43): a1a2, b2b1, a1b1, a1b2, a2b1, a2b2
-  const float* X[6] = {fa1, fb2, fa1, fa1, fa2, fa2};
-  const float* Y[6] = {fa2, fb1, fb1, fb2, fb1, fb2};
-  const float *xsq[6], *ysq[6];
-  if (cost_kind == OTGAN_COST_SQEUCLID_MEAN) {
-    hipLaunchKernelGGL(row_halfmeansq_kernel, dim3(ceil_div(2 * N, 4)), dim3(256), 0, s, fa, ldf,
-                       2 * N, D, w.sq_a);
-    hipLaunchKernelGGL(row_halfmeansq_kernel, dim3(ceil_div(2 * N, 4)), dim3(256), 0, s, fb, ldf,
-                       2 * N, D, w.sq_b);
-    const float *sa1 = w.sq_a, *sa2 = w.sq_a + N, *sb1 = w.sq_b, *sb2 = w.sq_b + N;
-    const float* xs[6] = {sa1, sb2, sa1, sa1, sa2, sa2};
-    const float* ys[6] = {sa2, sb1, sb1, sb2, sb1, sb2};
-    memcpy(xsq, xs, sizeof(xs));
-    memcpy(ysq, ys, sizeof(ys));
-  }
-  const bool x3 = w.x3 && cost_kind == OTGAN_COST_COSINE && ldf % 4 == 0 && aligned16(fa) && aligned16(fb);
-  int rc;
-  if (x3) {
-    // stacked rows: a1 [0,N) a2 [N,2N) b1 [2N,3N) b2 [3N,4N); problems a1a2, b2b1, a1b1, a1b2, a2b1, a2b2
-    const long xrow[6] = {0, 3L * N, 0, 0, N, N};
-    const long yrow[6] = {N, 2L * N, 2L * N, 3L * N, 2L * N, 3L * N};
-    ProfScope ps(OTGAN_PROF_COST_GEMM, 12.0 * N * (double)N * D, 16.0 * N * (double)D, s);
-    x3_split_features(w, fa, fb, 2 * N, D, ldf, s);
-    rc = launch_cost_x3(w.FP, w.planeF, 4L * N, xrow, yrow, nullptr, 6, N, N, D, lambda, w.partial, w.K, s);
-  } else {
-    rc = launch_cost(X, Y, cost_kind == OTGAN_COST_SQEUCLID_MEAN ? xsq : nullptr,
-                     cost_kind == OTGAN_COST_SQEUCLID_MEAN ? ysq : nullptr, nullptr, 6, N, N, D,
-                     ldf, lambda, cost_kind, w.partial, w.K, s);
-  }
+  // the toy cost stays on the exact-fp32 engine
+  const bool x3 = c.w.x3 && cost_kind == OTGAN_COST_COSINE && f.engine_ok();
+  rc = match_solve(c, x3, kStackArrays, f, cost_kind, toy ? sq : nullptr, nullptr,
+                   [&] { x3_split_features(c.w, fa, fb, 2 * N, D, ldf, c.s); });
   if (rc) return rc;
-  rc = launch_sinkhorn(w.K, 6, N, N, iters, lambda, w.plan, w.planT, w.stats, w.fg, s);
+  float* const out[4] = {f_aa, f_bb, f_ab, f_ba};
+  rc = apply_matched(c, x3 && ldo % 4 == 0, kMatchedTwoBatch, kStackArrays, f, 0, 1, 8, out, ldo, (long)N * ldo, 0, N);
   if (rc) return rc;
-  const size_t nn = (size_t)N * N;
-  const float *M0 = w.plan, *M1 = w.plan + nn, *M2 = w.plan + 2 * nn, *M3 = w.plan + 3 * nn,
-              *M4 = w.plan + 4 * nn, *M5 = w.plan + 5 * nn;
-  const float *T0 = w.planT, *T1 = w.planT + nn, *T2 = w.planT + 2 * nn, *T3 = w.planT + 3 * nn,
-              *T4 = w.planT + 4 * nn, *T5 = w.planT + 5 * nn;
-  // matching.py:64-83.  Eight [N,D] output blocks, each one or two plan.feature products.
-  ApplyBlock blk[8];
-  memset(blk, 0, sizeof(blk));
-  auto set1 = [&](int i, float* out, const float* P0, const float* F0, float alpha) {
-    blk[i].out = out; blk[i].rows = N; blk[i].nterms = 1; blk[i].alpha = alpha;
-    blk[i].t[0] = ApplyTerm{P0, F0, (long)N, N};
-  };
-  auto set2 = [&](int i, float* out, const float* P0, const float* F0, const float* P1,
-                  const float* F1, float alpha) {
-    blk[i].out = out; blk[i].rows = N; blk[i].nterms = 2; blk[i].alpha = alpha;
-    blk[i].t[0] = ApplyTerm{P0, F0, (long)N, N};
-    blk[i].t[1] = ApplyTerm{P1, F1, (long)N, N};
-  };
-  const long half = (long)N * ldo;
-  set1(0, f_aa, M0, fa2, 1.f);                  // a1 <- M_a1a2 . a2          (:64)
-  set1(1, f_aa + half, T0, fa1, 1.f);           // a2 <- M_a1a2^T . a1        (:70)
-  set1(2, f_bb, T1, fb2, 1.f);                  // b1 <- M_b2b1^T . b2        (:65)
-  set1(3, f_bb + half, M1, fb1, 1.f);           // b2 <- M_b2b1 . b1          (:71)
-  set2(4, f_ab, M2, fb1, M3, fb2, 0.5f);        // a1 <- (M_a1b1.b1 + M_a1b2.b2)/2   (:66,67,80)
-  set2(5, f_ab + half, M4, fb1, M5, fb2, 0.5f); // a2 <- (M_a2b1.b1 + M_a2b2.b2)/2   (:68,69,80)
-  set2(6, f_ba, T2, fa1, T4, fa2, 0.5f);        // b1 <- (M_a1b1^T.a1 + M_a2b1^T.a2)/2 (:72,74,82)
-  set2(7, f_ba + half, T3, fa1, T5, fa2, 0.5f); // b2 <- (M_a1b2^T.a1 + M_a2b2^T.a2)/2 (:73,75,82)
-  if (x3 && ldo % 4 == 0) {
-    // PT rows: T0 T1 T2 T3 T4 T5;  PM rows: M0 M1 M2 M4 M3 M5 (the pairs contracted together are adjacent)
-    const int orderM[6] = {0, 1, 2, 4, 3, 5};
-    const float alpha[6] = {1.f, 1.f, 0.5f, 0.5f, 0.5f, 0.5f};
-    x3_split_plans(w, w.plan, w.planT, 6, N, orderM, alpha, s);
-    const long n1 = N;
-    const X3ApplyBlock xb[8] = {
-        {w.PT, 0 * n1, 1 * n1, N, f_aa},            // a1 <- M0 . a2
-        {w.PM, 0 * n1, 0 * n1, N, f_aa + half},     // a2 <- M0^T . a1
-        {w.PM, 1 * n1, 3 * n1, N, f_bb},            // b1 <- M1^T . b2
-        {w.PT, 1 * n1, 2 * n1, N, f_bb + half},     // b2 <- M1 . b1
-        {w.PT, 2 * n1, 2 * n1, 2 * N, f_ab},        // a1 <- (M2 . b1 + M3 . b2) / 2
-        {w.PT, 4 * n1, 2 * n1, 2 * N, f_ab + half}, // a2 <- (M4 . b1 + M5 . b2) / 2
-        {w.PM, 2 * n1, 0 * n1, 2 * N, f_ba},        // b1 <- (M2^T . a1 + M4^T . a2) / 2
-        {w.PM, 4 * n1, 0 * n1, 2 * N, f_ba + half}, // b2 <- (M3^T . a1 + M5^T . a2) / 2
-    };
-    rc = launch_apply_x3(xb, 8, w.PT < w.PM ? w.PT : w.PM, x3_hdr(w.PT), w.planeP, N, w.FP, w.planeF, 0, N, D, ldo, s);
-  } else {
-    rc = launch_apply(blk, 8, N, D, ldf, ldo, s);
-  }
-  if (rc) return rc;
-  hipLaunchKernelGGL(entropy_finalize_kernel, dim3(1), dim3(1), 0, s, w.stats, 6, N, entropy);
   const double denom = (cost_kind == OTGAN_COST_COSINE) ? 2.0 * (2.0 * N)          // matching.py:152
                                                         : 2.0 * (2.0 * N) * (double)D;  // matching_cpu.py:158-163
-  rc = launch_distance(fa, fb, f_aa, f_bb, f_ab, (long)2 * N * D, denom, dist, w.dot3, s, w.stats, 6);
-  if (rc) return rc;
-  if (stats) hipMemcpyAsync(stats, w.stats, sizeof(double) * 24, hipMemcpyDeviceToDevice, s);
-  return OTGAN_OK;
+  return match_finish(c, entropy, stats, [&] { return distance_dot3(c, f, f_aa, f_bb, f_ab, denom, dist); });
 }
 
 int otgan_matching_two_batch_rows_f32(const float* fa, const float* fb, int N, int D, long ldf,
@@ -2135,95 +2289,21 @@ int otgan_matching_two_batch_rows_f32(const float* fa, const float* fb, int N, i
                                       float* f_ba, long ldo, float* entropy, double* dist,
                                       double* stats, void* workspace, size_t workspace_bytes,
                                       void* stream) {
+  const FeatSrc f = FeatSrc::arrays(fa, fb, ldf);
   OTGAN_CHECK_ARG(fa && fb && f_aa && f_bb && f_ab && f_ba && entropy && dist, "null pointer");
-  OTGAN_CHECK_ARG(N > 0 && D > 0 && ldf >= D && ldo >= D && iters >= 0, "bad sizes N=%d D=%d", N, D);
-  OTGAN_CHECK_ARG(row_begin >= 0 && row_count > 0 && row_begin + row_count <= 2 * N,
-                  "row range [%d, %d) outside [0, %d)", row_begin, row_begin + row_count, 2 * N);
-  const int half = row_begin / N;
-  OTGAN_CHECK_ARG((row_begin + row_count - 1) / N == half, "row range must not straddle the two mini-batches");
-  hipStream_t s = (hipStream_t)stream;
-  MatchWs w = carve_match(workspace, workspace_bytes, 6, N, D, 2 * N);
-  if (!workspace || workspace_bytes < w.bytes) {
-    otgan_set_error("workspace too small: need %zu bytes, got %zu", w.bytes, workspace_bytes);
-    return OTGAN_ERR_WORKSPACE;
-  }
-  const float *fa1 = fa, *fa2 = fa + (long)N * ldf, *fb1 = fb, *fb2 = fb + (long)N * ldf;
-  const float* X[6] = {fa1, fb2, fa1, fa1, fa2, fa2};
-  const float* Y[6] = {fa2, fb1, fb1, fb2, fb1, fb2};
-  int rc = OTGAN_OK;
-  const float* Kuse = K_pre;
-  const bool x3 = w.x3 && ldf % 4 == 0 && ldo % 4 == 0 && aligned16(fa) && aligned16(fb) && row_begin % 16 == 0;
-  if (x3) x3_split_features(w, fa, fb, 2 * N, D, ldf, s);     // cost operand and B operand of the plan application
-  if (!K_pre) {
-    if (x3) {
-      const long xrow[6] = {0, 3L * N, 0, 0, N, N};
-      const long yrow[6] = {N, 2L * N, 2L * N, 3L * N, 2L * N, 3L * N};
-      ProfScope ps(OTGAN_PROF_COST_GEMM, 12.0 * N * (double)N * D, 16.0 * N * (double)D, s);
-      rc = launch_cost_x3(w.FP, w.planeF, 4L * N, xrow, yrow, nullptr, 6, N, N, D, lambda, w.partial, w.K, s);
-    } else {
-      rc = launch_cost(X, Y, nullptr, nullptr, nullptr, 6, N, N, D, ldf, lambda, OTGAN_COST_COSINE,
-                       w.partial, w.K, s);
-    }
-    if (rc) return rc;
-    Kuse = w.K;
-  }
-  rc = launch_sinkhorn(Kuse, 6, N, N, iters, lambda, w.plan, w.planT, w.stats, w.fg, s);
+  int rc = match_check_sizes("N", N, D, f, ldo, iters);
+  if (rc || (rc = match_check_rows(row_begin, row_count, 2 * N, N))) return rc;
+  MatchCall c = {kTwoBatch, N, D, lambda, iters, (hipStream_t)stream};
+  if ((rc = match_begin(c, false, workspace, workspace_bytes))) return rc;
+  const int half = row_begin / N;      // rows of a1 / b1 (matching.py:64-67,72,74) or of a2 / b2 (:68-71,73,75)
+  const bool x3 = c.w.x3 && f.engine_ok() && ldo % 4 == 0 && row_begin % 16 == 0;
+  if (x3) x3_split_features(c.w, fa, fb, 2 * N, D, ldf, c.s);     // cost operand and B operand of the plan application
+  rc = match_solve(c, x3, kStackArrays, f, K_pre);
   if (rc) return rc;
-  const size_t nn = (size_t)N * N;
-  const long ro = (long)(row_begin - half * N) * N;  // first plan row of the range
-  const float* M[6];
-  const float* T[6];
-  for (int p = 0; p < 6; ++p) {
-    M[p] = w.plan + p * nn + ro;
-    T[p] = w.planT + p * nn + ro;
-  }
-  ApplyBlock blk[4];
-  memset(blk, 0, sizeof(blk));
-  auto set = [&](int i, float* out, const float* P0, const float* F0, const float* P1, const float* F1,
-                 float alpha) {
-    blk[i].out = out; blk[i].rows = row_count; blk[i].nterms = P1 ? 2 : 1; blk[i].alpha = alpha;
-    blk[i].t[0] = ApplyTerm{P0, F0, (long)N, N};
-    if (P1) blk[i].t[1] = ApplyTerm{P1, F1, (long)N, N};
-  };
-  if (half == 0) {  // rows of a1 / b1  (matching.py:64-67,72,74)
-    set(0, f_aa, M[0], fa2, nullptr, nullptr, 1.f);
-    set(1, f_bb, T[1], fb2, nullptr, nullptr, 1.f);
-    set(2, f_ab, M[2], fb1, M[3], fb2, 0.5f);
-    set(3, f_ba, T[2], fa1, T[4], fa2, 0.5f);
-  } else {          // rows of a2 / b2  (matching.py:68-71,73,75)
-    set(0, f_aa, T[0], fa1, nullptr, nullptr, 1.f);
-    set(1, f_bb, M[1], fb1, nullptr, nullptr, 1.f);
-    set(2, f_ab, M[4], fb1, M[5], fb2, 0.5f);
-    set(3, f_ba, T[3], fa1, T[5], fa2, 0.5f);
-  }
-  if (x3) {
-    const int orderM[6] = {0, 1, 2, 4, 3, 5};
-    const float alpha[6] = {1.f, 1.f, 0.5f, 0.5f, 0.5f, 0.5f};
-    x3_split_plans(w, w.plan, w.planT, 6, N, orderM, alpha, s);
-    const long n1 = N;
-    const int r0 = row_begin - half * N;
-    X3ApplyBlock xb[4];
-    if (half == 0) {  // rows of a1 / b1
-      xb[0] = {w.PT, 0 * n1, 1 * n1, N, f_aa};         // M0 . a2
-      xb[1] = {w.PM, 1 * n1, 3 * n1, N, f_bb};         // M1^T . b2
-      xb[2] = {w.PT, 2 * n1, 2 * n1, 2 * N, f_ab};     // (M2 . b1 + M3 . b2) / 2
-      xb[3] = {w.PM, 2 * n1, 0 * n1, 2 * N, f_ba};     // (M2^T . a1 + M4^T . a2) / 2
-    } else {          // rows of a2 / b2
-      xb[0] = {w.PM, 0 * n1, 0 * n1, N, f_aa};         // M0^T . a1
-      xb[1] = {w.PT, 1 * n1, 2 * n1, N, f_bb};         // M1 . b1
-      xb[2] = {w.PT, 4 * n1, 2 * n1, 2 * N, f_ab};     // (M4 . b1 + M5 . b2) / 2
-      xb[3] = {w.PM, 4 * n1, 0 * n1, 2 * N, f_ba};     // (M3^T . a1 + M5^T . a2) / 2
-    }
-    rc = launch_apply_x3(xb, 4, w.PT < w.PM ? w.PT : w.PM, x3_hdr(w.PT), w.planeP, N, w.FP, w.planeF, r0, row_count, D, ldo, s);
-  } else {
-    rc = launch_apply(blk, 4, row_count, D, ldf, ldo, s);
-  }
+  float* const out[4] = {f_aa, f_bb, f_ab, f_ba};
+  rc = apply_matched(c, x3, kMatchedTwoBatch, kStackArrays, f, half, 2, 4, out, ldo, 0, row_begin - half * N, row_count);
   if (rc) return rc;
-  hipLaunchKernelGGL(entropy_finalize_kernel, dim3(1), dim3(1), 0, s, w.stats, 6, N, entropy);
-  hipLaunchKernelGGL(closed_form_distance_kernel, dim3(1), dim3(1), 0, s, w.stats, N, dist);
-  OTGAN_CHECK_LAUNCH("matching finalize");
-  if (stats) hipMemcpyAsync(stats, w.stats, sizeof(double) * 24, hipMemcpyDeviceToDevice, s);
-  return OTGAN_OK;
+  return match_finish(c, entropy, stats, [&] { return distance_closed_two_batch(c, dist); });
 }
 
 // ---- training-mode matching: the injected gradients directly (round 3) ---------------------------------------
@@ -2236,72 +2316,36 @@ int otgan_matching_two_batch_rows_f32(const float* fa, const float* fb, int N, i
 // of six, which need no data-side gradient) replace eight, the four [2N, D] matched arrays are never written, the two
 // subtractions disappear, and the distance comes from the Sinkhorn kernel's statistics (closed form) instead of a pass
 // over five [2N, D] arrays.
-static int matching_grad_impl(const float* fa, const float* fb, int N, int D, long ldf, float lambda, int iters,
-                              int row_begin, int row_count, const float* K_pre, float* grad_a, float* grad_b, long ldo,
-                              float* entropy, double* dist, double* stats, void* workspace, size_t workspace_bytes,
-                              void* stream, const void* stack = nullptr) {
-  OTGAN_CHECK_ARG((stack || (fa && fb)) && grad_a && entropy && dist, "null pointer");
-  OTGAN_CHECK_ARG(N > 0 && D > 0 && ldf >= D && ldo >= D && iters >= 0, "bad sizes N=%d D=%d", N, D);
-  OTGAN_CHECK_ARG(row_begin >= 0 && row_count > 0 && row_begin + row_count <= 2 * N,
-                  "row range [%d, %d) outside [0, %d)", row_begin, row_begin + row_count, 2 * N);
+static int matching_grad_impl(const FeatSrc& f, int N, int D, float lambda, int iters, int row_begin, int row_count,
+                              const float* K_pre, float* grad_a, float* grad_b, long ldo, float* entropy, double* dist,
+                              double* stats, void* workspace, size_t workspace_bytes, void* stream) {
+  OTGAN_CHECK_ARG(f.given() && grad_a && entropy && dist, "null pointer");
+  int rc = match_check_sizes("N", N, D, f, ldo, iters);
   const bool full = row_begin == 0 && row_count == 2 * N;
+  if (rc || (rc = match_check_rows(row_begin, row_count, 2 * N, full ? 0 : N))) return rc;
   const int half = row_begin / N;
-  OTGAN_CHECK_ARG(full || (row_begin + row_count - 1) / N == half, "row range must not straddle the two mini-batches");
-  hipStream_t s = (hipStream_t)stream;
-  MatchWs w = carve_match(workspace, workspace_bytes, 6, N, D, 2 * N, true);
-  if (!workspace || workspace_bytes < w.bytes) {
-    otgan_set_error("workspace too small: need %zu bytes, got %zu", w.bytes, workspace_bytes);
-    return OTGAN_ERR_WORKSPACE;
-  }
-  const float *fa1 = fa, *fa2 = fa + (long)N * ldf, *fb1 = fb, *fb2 = fb + (long)N * ldf;
-  const float* X[6] = {fa1, fb2, fa1, fa1, fa2, fa2};
-  const float* Y[6] = {fa2, fb1, fb1, fb2, fb1, fb2};
-  int rc = OTGAN_OK;
-  const bool x3 = w.x3 && ldf % 4 == 0 && ldo % 4 == 0 && aligned16(fa) && aligned16(fb) && aligned16(grad_a) &&
-                  aligned16(grad_b) && row_begin % 16 == 0;
-  const int nstack = grad_b ? 6 : 4;
-  if (stack) {
+  MatchCall c = {kTwoBatch, N, D, lambda, iters, (hipStream_t)stream};
+  if ((rc = match_begin(c, true, workspace, workspace_bytes))) return rc;
+  MatchWs& w = c.w;
+  hipStream_t s = c.s;
+  const bool x3 = w.x3 && f.engine_ok() && ldo % 4 == 0 && aligned16(grad_a) && aligned16(grad_b) && row_begin % 16 == 0;
+  const StackLayout lay = kStackGrad.first(grad_b ? 6 : 4);
+  if (f.stack) {
     // the caller split the blocks this call reads already (otgan_matching_stack_split_f32): same layout, its own buffer
     OTGAN_CHECK_ARG(x3 && K_pre, "a feature stack needs the split-precision engine's shapes / alignment and precomputed log-kernels");
-    w.FP = (u16*)((char*)const_cast<void*>(stack) + kX3HdrBytes);
+    w.FP = (u16*)((char*)const_cast<void*>(f.stack) + kX3HdrBytes);
   } else if (x3) {
-    // stacked feature operand [a1 b1 b2 a2 (a1 b1)]: every difference contracts over three ADJACENT blocks
     SplitSrc ss;
     memset(&ss, 0, sizeof(ss));
-    const float* blocks[6] = {fa1, fb1, fb2, fa2, fa1, fb1};
-    ss.n = nstack;
-    for (int i = 0; i < nstack; ++i) { ss.src[i] = blocks[i]; ss.ld[i] = ldf; ss.row0[i] = (long)i * N; ss.scale[i] = 1.f; }
+    ss.n = lay.nblocks;
+    for (int i = 0; i < ss.n; ++i) { ss.src[i] = f.block(lay.block[i], N); ss.ld[i] = f.ld; ss.row0[i] = (long)i * N; ss.scale[i] = 1.f; }
     x3_split(ss, N, D, w.FP, w.planeF, kX3FeatureExp, s);
   }
-  const float* Kuse = K_pre;
-  if (!K_pre) {
-    if (x3) {
-      // rows of the stack: a1 0, b1 N, b2 2N, a2 3N
-      const long xrow[6] = {0, 2L * N, 0, 0, 3L * N, 3L * N};
-      const long yrow[6] = {3L * N, N, N, 2L * N, N, 2L * N};
-      ProfScope ps(OTGAN_PROF_COST_GEMM, 12.0 * N * (double)N * D, 16.0 * N * (double)D, s);
-      rc = launch_cost_x3(w.FP, w.planeF, (long)nstack * N, xrow, yrow, nullptr, 6, N, N, D, lambda, w.partial, w.K, s);
-    } else {
-      rc = launch_cost(X, Y, nullptr, nullptr, nullptr, 6, N, N, D, ldf, lambda, OTGAN_COST_COSINE, w.partial, w.K, s);
-    }
-    if (rc) return rc;
-    Kuse = w.K;
-  }
-  rc = launch_sinkhorn(Kuse, 6, N, N, iters, lambda, w.plan, w.planT, w.stats, w.fg, s);
+  rc = match_solve(c, x3, lay, f, K_pre);
   if (rc) return rc;
   const size_t nn = (size_t)N * N;
   const float *M[6], *T[6];
   for (int p = 0; p < 6; ++p) { M[p] = w.plan + p * nn; T[p] = w.planT + p * nn; }
-  // the four differences: {unit-weight plan, its features, the two half-weight plans and their features}
-  struct Diff {
-    const float *P0, *F0, *P1, *F1, *P2, *F2;
-  };
-  const Diff diff[4] = {
-      {M[0], fa2, M[2], fb1, M[3], fb2},   // g(a1)   (matching.py:64,66,67,80)
-      {T[0], fa1, M[4], fb1, M[5], fb2},   // g(a2)   (:70,68,69,80)
-      {T[1], fb2, T[2], fa1, T[4], fa2},   // g(b1)   (:65,72,74,82)
-      {M[1], fb1, T[3], fa1, T[5], fa2},   // g(b2)   (:71,73,75,82)
-  };
   // output blocks of this call: which difference, where it goes, which plan rows
   int which[4], nblk = 0;
   float* outp[4];
@@ -2339,6 +2383,17 @@ static int matching_grad_impl(const float* fa, const float* fb, int N, int D, lo
     for (int z = 0; z < nblk; ++z) xb[z] = X3ApplyBlock{w.PT, 3L * z * N, frow[which[z]], 3 * N, outp[z]};
     rc = launch_apply_x3(xb, nblk, w.PT, x3_hdr(w.PT), w.planeP, N, w.FP, w.planeF, r0, cnt, D, ldo, s);
   } else {
+    // the four differences: {unit-weight plan, its features, the two half-weight plans and their features}
+    struct Diff {
+      const float *P0, *F0, *P1, *F1, *P2, *F2;
+    };
+    const float *fa1 = f.block(A1, N), *fa2 = f.block(A2, N), *fb1 = f.block(B1, N), *fb2 = f.block(B2, N);
+    const Diff diff[4] = {
+        {M[0], fa2, M[2], fb1, M[3], fb2},   // g(a1)   (matching.py:64,66,67,80)
+        {T[0], fa1, M[4], fb1, M[5], fb2},   // g(a2)   (:70,68,69,80)
+        {T[1], fb2, T[2], fa1, T[4], fa2},   // g(b1)   (:65,72,74,82)
+        {M[1], fb1, T[3], fa1, T[5], fa2},   // g(b2)   (:71,73,75,82)
+    };
     ApplyBlock blk[4];
     memset(blk, 0, sizeof(blk));
     const long ro = (long)r0 * N;
@@ -2350,14 +2405,10 @@ static int matching_grad_impl(const float* fa, const float* fb, int N, int D, lo
       blk[z].t[2] = ApplyTerm{d.P0 + ro, d.F0, (long)N, N};
       blk[z].rescale[2] = -0.5f;
     }
-    rc = launch_apply(blk, nblk, cnt, D, ldf, ldo, s);
+    rc = launch_apply(blk, nblk, cnt, D, f.ld, ldo, s);
   }
   if (rc) return rc;
-  hipLaunchKernelGGL(entropy_finalize_kernel, dim3(1), dim3(1), 0, s, w.stats, 6, N, entropy);
-  hipLaunchKernelGGL(closed_form_distance_kernel, dim3(1), dim3(1), 0, s, w.stats, N, dist);
-  OTGAN_CHECK_LAUNCH("matching finalize");
-  if (stats) hipMemcpyAsync(stats, w.stats, sizeof(double) * 24, hipMemcpyDeviceToDevice, s);
-  return OTGAN_OK;
+  return match_finish(c, entropy, stats, [&] { return distance_closed_two_batch(c, dist); });
 }
 
 // ---- one split of the features per step for a data-parallel rank (round 5) ------------------------------------------
@@ -2370,7 +2421,7 @@ static int matching_grad_impl(const float* fa, const float* fb, int N, int D, lo
 // of its cost slices AND the contraction blocks of g(a1)) plus its own rows of a1 -- once, and hands it to both calls.
 size_t otgan_matching_stack_bytes(int N, int D) {
   if (N <= 0 || D <= 0 || !x3_shape_ok(N, N, D)) return 0;
-  return kX3HdrBytes + sizeof(u16) * X3_NP * x3_plane_elems(6 * (size_t)N, D);
+  return kX3HdrBytes + sizeof(u16) * X3_NP * x3_plane_elems(kStackGrad.nblocks * (size_t)N, D);
 }
 int otgan_matching_stack_split_f32(const float* fa, const float* fb, int N, int D, long ldf, int nranges,
                                    const int* range_begin, const int* range_rows, void* stack, void* stream) {
@@ -2379,10 +2430,11 @@ int otgan_matching_stack_split_f32(const float* fa, const float* fb, int N, int 
                   "shape N=%d D=%d not taken by the split-precision engine (otgan_matching_stack_bytes == 0) or unaligned", N, D);
   OTGAN_CHECK_ARG(nranges > 0 && nranges <= 6, "1 .. 6 row ranges");
   hipStream_t s = (hipStream_t)stream;
-  const float *fa1 = fa, *fa2 = fa + (long)N * ldf, *fb1 = fb, *fb2 = fb + (long)N * ldf;
-  const float* blocks[6] = {fa1, fb1, fb2, fa2, fa1, fb1};
+  const FeatSrc f = FeatSrc::arrays(fa, fb, ldf);
+  const float* blocks[6];
+  for (int i = 0; i < kStackGrad.nblocks; ++i) blocks[i] = f.block(kStackGrad.block[i], N);
   u16* FP = (u16*)((char*)stack + kX3HdrBytes);
-  const long plane = (long)x3_plane_elems(6 * (size_t)N, D);
+  const long plane = (long)x3_plane_elems(kStackGrad.nblocks * (size_t)N, D);
   // one job per (range, block it touches): a job's sources share a row count
   X3SplitJob jobs[12];
   int nj = 0;
@@ -2423,13 +2475,10 @@ int otgan_cost_slices_stack_f32(const void* stack, int N, int D, int P, const lo
     OTGAN_CHECK_ARG(xrow[p] >= 0 && xrow[p] % 32 == 0 && xrow[p] + nrows <= 6L * N && yrow[p] >= 0 && yrow[p] % N == 0 && yrow[p] < 6L * N,
                     "problem %d: rows outside the stack", p);
   const size_t need = otgan_cost_slices_stack_workspace_bytes(P, nrows, N, D);
-  if (!workspace || workspace_bytes < need) {
-    otgan_set_error("workspace too small: need %zu bytes, got %zu", need, workspace_bytes);
-    return OTGAN_ERR_WORKSPACE;
-  }
+  if (int rc = check_workspace(workspace, workspace_bytes, need)) return rc;
   hipStream_t s = (hipStream_t)stream;
   const u16* FP = (const u16*)((const char*)stack + kX3HdrBytes);
-  const long plane = (long)x3_plane_elems(6 * (size_t)N, D);
+  const long plane = (long)x3_plane_elems(kStackGrad.nblocks * (size_t)N, D);
   ProfScope ps(OTGAN_PROF_COST_GEMM, 2.0 * P * nrows * (double)N * D, 4.0 * P * ((double)nrows + N) * D, s);
   return launch_cost_x3(FP, plane, 6L * N, xrow, yrow, nullptr, P, nrows, N, D, lambda, (float*)workspace, K, s);
 }
@@ -2439,10 +2488,8 @@ int otgan_matching_two_batch_rows_grad_stack_f32(const void* stack, int N, int D
                                                  size_t workspace_bytes, void* stream) {
   OTGAN_CHECK_ARG(stack, "null stack");
   OTGAN_CHECK_ARG(!(row_begin == 0 && row_count == 2 * N), "the row-range variant takes a range inside one mini-batch");
-  // (the feature pointers only serve the alignment test of the shared implementation)
-  const float* aligned = reinterpret_cast<const float*>(stack);
-  return matching_grad_impl(aligned, aligned, N, D, D, lambda, iters, row_begin, row_count, K_pre, grad_a, grad_b, ldo, entropy,
-                            dist, stats, workspace, workspace_bytes, stream, stack);
+  return matching_grad_impl(FeatSrc::presplit(stack), N, D, lambda, iters, row_begin, row_count, K_pre, grad_a, grad_b, ldo, entropy,
+                            dist, stats, workspace, workspace_bytes, stream);
 }
 
 size_t otgan_matching_grad_workspace_bytes(int N, int D) {
@@ -2452,7 +2499,7 @@ size_t otgan_matching_grad_workspace_bytes(int N, int D) {
 int otgan_matching_two_batch_grad_f32(const float* fa, const float* fb, int N, int D, long ldf, float lambda, int iters,
                                       float* grad_a, float* grad_b, long ldo, float* entropy, double* dist,
                                       double* stats, void* workspace, size_t workspace_bytes, void* stream) {
-  return matching_grad_impl(fa, fb, N, D, ldf, lambda, iters, 0, 2 * N, nullptr, grad_a, grad_b, ldo, entropy, dist, stats,
+  return matching_grad_impl(FeatSrc::arrays(fa, fb, ldf), N, D, lambda, iters, 0, 2 * N, nullptr, grad_a, grad_b, ldo, entropy, dist, stats,
                             workspace, workspace_bytes, stream);
 }
 int otgan_matching_two_batch_rows_grad_f32(const float* fa, const float* fb, int N, int D, long ldf, float lambda,
@@ -2460,7 +2507,7 @@ int otgan_matching_two_batch_rows_grad_f32(const float* fa, const float* fb, int
                                            float* grad_b, long ldo, float* entropy, double* dist, double* stats,
                                            void* workspace, size_t workspace_bytes, void* stream) {
   OTGAN_CHECK_ARG(!(row_begin == 0 && row_count == 2 * N), "the row-range variant takes a range inside one mini-batch");
-  return matching_grad_impl(fa, fb, N, D, ldf, lambda, iters, row_begin, row_count, K_pre, grad_a, grad_b, ldo, entropy,
+  return matching_grad_impl(FeatSrc::arrays(fa, fb, ldf), N, D, lambda, iters, row_begin, row_count, K_pre, grad_a, grad_b, ldo, entropy,
                             dist, stats, workspace, workspace_bytes, stream);
 }
 
@@ -2469,65 +2516,21 @@ int otgan_matching_single_batch_f32(const float* fa, const float* fb, int n, int
                                     float* f_ab, float* f_ba, long ldo, float* entropy,
                                     double* dist, double* stats, void* workspace,
                                     size_t workspace_bytes, void* stream) {
+  const FeatSrc f = FeatSrc::arrays(fa, fb, ldf);
   OTGAN_CHECK_ARG(fa && fb && f_aa && f_bb && f_ab && f_ba && entropy && dist, "null pointer");
-  OTGAN_CHECK_ARG(n > 0 && D > 0 && ldf >= D && ldo >= D && iters >= 0, "bad sizes n=%d D=%d", n, D);
+  int rc = match_check_sizes("n", n, D, f, ldo, iters);
+  if (rc) return rc;
   OTGAN_CHECK_ARG(ldf == D && ldo == D, "feature arrays must be contiguous (ld == D)");
-  hipStream_t s = (hipStream_t)stream;
-  MatchWs w = carve_match(workspace, workspace_bytes, 3, n, D, n);
-  if (!workspace || workspace_bytes < w.bytes) {
-    otgan_set_error("workspace too small: need %zu bytes, got %zu", w.bytes, workspace_bytes);
-    return OTGAN_ERR_WORKSPACE;
-  }
-  const float* X[3] = {fa, fb, fa};
-  const float* Y[3] = {fa, fb, fb};
-  const float diag[3] = {999.f, 999.f, 0.f};  // matching.py:109-110
-  const bool x3 = w.x3 && ldf % 4 == 0 && ldo % 4 == 0 && aligned16(fa) && aligned16(fb);
-  int rc;
-  if (x3) {   // stacked rows: a [0,n), b [n,2n); problems aa, bb, ab
-    const long xrow[3] = {0, n, 0};
-    const long yrow[3] = {0, n, n};
-    ProfScope ps(OTGAN_PROF_COST_GEMM, 6.0 * n * (double)n * D, 8.0 * n * (double)D, s);
-    x3_split_features(w, fa, fb, n, D, ldf, s);
-    rc = launch_cost_x3(w.FP, w.planeF, 2L * n, xrow, yrow, diag, 3, n, n, D, lambda, w.partial, w.K, s);
-  } else {
-    rc = launch_cost(X, Y, nullptr, nullptr, diag, 3, n, n, D, ldf, lambda, OTGAN_COST_COSINE,
-                     w.partial, w.K, s);
-  }
+  MatchCall c = {kSingleBatch, n, D, lambda, iters, (hipStream_t)stream};
+  if ((rc = match_begin(c, false, workspace, workspace_bytes))) return rc;
+  const bool x3 = c.w.x3 && f.engine_ok() && ldo % 4 == 0;
+  rc = match_solve(c, x3, kStackSingle, f, OTGAN_COST_COSINE, nullptr, nullptr,
+                   [&] { x3_split_features(c.w, fa, fb, n, D, ldf, c.s); });
   if (rc) return rc;
-  rc = launch_sinkhorn(w.K, 3, n, n, iters, lambda, w.plan, w.planT, w.stats, w.fg, s);
+  float* const out[4] = {f_aa, f_bb, f_ab, f_ba};
+  rc = apply_matched(c, x3, kMatchedSingle, kStackSingle, f, 0, 1, 4, out, ldo, 0, 0, n);
   if (rc) return rc;
-  const size_t nn = (size_t)n * n;
-  ApplyBlock blk[4];
-  memset(blk, 0, sizeof(blk));
-  auto set1 = [&](int i, float* out, const float* P0, const float* F0) {
-    blk[i].out = out; blk[i].rows = n; blk[i].nterms = 1; blk[i].alpha = 1.f;
-    blk[i].t[0] = ApplyTerm{P0, F0, (long)n, n};
-  };
-  set1(0, f_aa, w.plan, fa);            // :131
-  set1(1, f_bb, w.plan + nn, fb);       // :132
-  set1(2, f_ab, w.plan + 2 * nn, fb);   // :133
-  set1(3, f_ba, w.planT + 2 * nn, fa);  // :134
-  if (x3) {
-    const int orderM[3] = {0, 1, 2};
-    const float alpha[3] = {1.f, 1.f, 1.f};
-    x3_split_plans(w, w.plan, w.planT, 3, n, orderM, alpha, s);
-    const long n1 = n;
-    const X3ApplyBlock xb[4] = {
-        {w.PT, 0 * n1, 0 * n1, n, f_aa},     // M_aa . a
-        {w.PT, 1 * n1, 1 * n1, n, f_bb},     // M_bb . b
-        {w.PT, 2 * n1, 1 * n1, n, f_ab},     // M_ab . b
-        {w.PM, 2 * n1, 0 * n1, n, f_ba},     // M_ab^T . a
-    };
-    rc = launch_apply_x3(xb, 4, w.PT < w.PM ? w.PT : w.PM, x3_hdr(w.PT), w.planeP, n, w.FP, w.planeF, 0, n, D, ldo, s);
-  } else {
-    rc = launch_apply(blk, 4, n, D, ldf, ldo, s);
-  }
-  if (rc) return rc;
-  hipLaunchKernelGGL(entropy_finalize_kernel, dim3(1), dim3(1), 0, s, w.stats, 3, n, entropy);
-  rc = launch_distance(fa, fb, f_aa, f_bb, f_ab, (long)n * D, 2.0 * n, dist, w.dot3, s, w.stats, 3);
-  if (rc) return rc;
-  if (stats) hipMemcpyAsync(stats, w.stats, sizeof(double) * 12, hipMemcpyDeviceToDevice, s);
-  return OTGAN_OK;
+  return match_finish(c, entropy, stats, [&] { return distance_dot3(c, f, f_aa, f_bb, f_ab, 2.0 * n, dist); });
 }
 
 // Training-mode single-batch matching: the injected gradients f_aa - f_ab (train.py:111) and f_bb - f_ba (train.py:125-126)
@@ -2537,37 +2540,17 @@ int otgan_matching_single_batch_f32(const float* fa, const float* fb, int n, int
 static int single_grad_impl(const float* fa, const float* fb, int n, int D, long ldf, float lambda, int iters, int row_begin,
                             int row_count, const float* K_pre, float* grad_a, float* grad_b, long ldo, float* entropy,
                             double* dist, double* stats, void* workspace, size_t workspace_bytes, void* stream) {
+  const FeatSrc f = FeatSrc::arrays(fa, fb, ldf);
   OTGAN_CHECK_ARG(fa && fb && grad_a && entropy && dist, "null pointer");
-  OTGAN_CHECK_ARG(n > 0 && D > 0 && ldf >= D && ldo >= D && iters >= 0, "bad sizes n=%d D=%d", n, D);
-  OTGAN_CHECK_ARG(row_begin >= 0 && row_count > 0 && row_begin + row_count <= n,
-                  "row range [%d, %d) outside [0, %d)", row_begin, row_begin + row_count, n);
-  hipStream_t s = (hipStream_t)stream;
-  MatchWs w = carve_match(workspace, workspace_bytes, 3, n, D, n, true);
-  if (!workspace || workspace_bytes < w.bytes) {
-    otgan_set_error("workspace too small: need %zu bytes, got %zu", w.bytes, workspace_bytes);
-    return OTGAN_ERR_WORKSPACE;
-  }
-  const float* X[3] = {fa, fb, fa};
-  const float* Y[3] = {fa, fb, fb};
-  const float diag[3] = {999.f, 999.f, 0.f};  // matching.py:109-110
-  const bool x3 = w.x3 && ldf % 4 == 0 && ldo % 4 == 0 && aligned16(fa) && aligned16(fb) && aligned16(grad_a) &&
-                  aligned16(grad_b) && row_begin % 16 == 0;
-  int rc = OTGAN_OK;
-  if (x3) x3_split_features(w, fa, fb, n, D, ldf, s);   // stacked rows: a [0, n), b [n, 2n)
-  const float* Kuse = K_pre;
-  if (!K_pre) {
-    if (x3) {
-      const long xrow[3] = {0, n, 0};
-      const long yrow[3] = {0, n, n};
-      ProfScope ps(OTGAN_PROF_COST_GEMM, 6.0 * n * (double)n * D, 8.0 * n * (double)D, s);
-      rc = launch_cost_x3(w.FP, w.planeF, 2L * n, xrow, yrow, diag, 3, n, n, D, lambda, w.partial, w.K, s);
-    } else {
-      rc = launch_cost(X, Y, nullptr, nullptr, diag, 3, n, n, D, ldf, lambda, OTGAN_COST_COSINE, w.partial, w.K, s);
-    }
-    if (rc) return rc;
-    Kuse = w.K;
-  }
-  rc = launch_sinkhorn(Kuse, 3, n, n, iters, lambda, w.plan, w.planT, w.stats, w.fg, s);
+  int rc = match_check_sizes("n", n, D, f, ldo, iters);
+  if (rc || (rc = match_check_rows(row_begin, row_count, n, 0))) return rc;
+  MatchCall c = {kSingleBatch, n, D, lambda, iters, (hipStream_t)stream};
+  if ((rc = match_begin(c, true, workspace, workspace_bytes))) return rc;
+  const MatchWs& w = c.w;
+  hipStream_t s = c.s;
+  const bool x3 = w.x3 && f.engine_ok() && ldo % 4 == 0 && aligned16(grad_a) && aligned16(grad_b) && row_begin % 16 == 0;
+  if (x3) x3_split_features(w, fa, fb, n, D, ldf, s);
+  rc = match_solve(c, x3, kStackSingle, f, K_pre);
   if (rc) return rc;
   const size_t nn = (size_t)n * n;
   const float *M[3], *T[3];
@@ -2605,11 +2588,12 @@ static int single_grad_impl(const float* fa, const float* fb, int n, int D, long
     rc = launch_apply(blk, nblk, row_count, D, ldf, ldo, s);
   }
   if (rc) return rc;
-  hipLaunchKernelGGL(entropy_finalize_kernel, dim3(1), dim3(1), 0, s, w.stats, 3, n, entropy);
-  hipLaunchKernelGGL(closed_form_single_distance_kernel, dim3(1), dim3(256), 0, s, w.stats, w.plan, n, (double)diag[0], dist);
-  OTGAN_CHECK_LAUNCH("single-batch matching finalize");
-  if (stats) hipMemcpyAsync(stats, w.stats, sizeof(double) * 12, hipMemcpyDeviceToDevice, s);
-  return OTGAN_OK;
+  return match_finish(c, entropy, stats, [&] {
+    hipLaunchKernelGGL(closed_form_single_distance_kernel, dim3(1), dim3(256), 0, s, w.stats, w.plan, n,
+                       (double)kSingleBatch.diag[0], dist);
+    OTGAN_CHECK_LAUNCH("single-batch matching finalize");
+    return (int)OTGAN_OK;
+  });
 }
 
 size_t otgan_matching_single_batch_grad_workspace_bytes(int n, int D) {
@@ -2635,8 +2619,7 @@ int otgan_matching_single_batch_rows_grad_f32(const float* fa, const float* fb, 
 static size_t cost_batched_ws(int P, int n, int m, int D, bool* x3_out) {
   const bool x3 = x3_shape_ok(n, m, D);
   if (x3_out) *x3_out = x3;
-  int nsplit = plan_cost(P, n, m, D).nsplit;
-  if (x3 && x3_plan_cost(P, n, m, D).nsplit > nsplit) nsplit = x3_plan_cost(P, n, m, D).nsplit;
+  const int nsplit = cost_partial_splits(P, n, m, D, x3);
   size_t b = align_up(sizeof(float) * (size_t)P * n * m * nsplit, 256) + (size_t)P * (align_up(sizeof(float) * n, 256) +
                                                                                       align_up(sizeof(float) * m, 256));
   if (x3) b += align_up(kX3HdrBytes + sizeof(u16) * X3_NP * x3_plane_elems((size_t)P * ((size_t)n + m), D), 256);
@@ -2663,13 +2646,9 @@ int otgan_cost_matrix_batched_f32(const float* const* X, const float* const* Y, 
   for (int p = 0; p < P; ++p) OTGAN_CHECK_ARG(X[p] && Y[p], "null block pointer");
   bool x3 = false;
   const size_t need = cost_batched_ws(P, n, m, D, &x3);
-  if (!workspace || workspace_bytes < need) {
-    otgan_set_error("workspace too small: need %zu bytes, got %zu", need, workspace_bytes);
-    return OTGAN_ERR_WORKSPACE;
-  }
+  if (int rc = check_workspace(workspace, workspace_bytes, need)) return rc;
   hipStream_t s = (hipStream_t)stream;
-  int nsplit = plan_cost(P, n, m, D).nsplit;
-  if (x3 && x3_plan_cost(P, n, m, D).nsplit > nsplit) nsplit = x3_plan_cost(P, n, m, D).nsplit;
+  const int nsplit = cost_partial_splits(P, n, m, D, x3);
   Carver c(workspace, workspace_bytes);
   float* partial = (float*)c.take(sizeof(float) * (size_t)P * n * m * nsplit);
   const float *xp[kMaxProb], *yp[kMaxProb];
@@ -2739,10 +2718,7 @@ int otgan_sinkhorn_plan_f32(const float* K, int P, int n, int m, int iters, floa
   OTGAN_CHECK_ARG(K && plan && planT && stats, "null pointer");
   OTGAN_CHECK_ARG(P > 0 && n > 0 && m > 0 && iters >= 0 && lambda != 0.f, "bad sizes");
   const size_t need = otgan_sinkhorn_workspace_bytes(P, n, m);
-  if (!workspace || workspace_bytes < need) {
-    otgan_set_error("workspace too small: need %zu bytes, got %zu", need, workspace_bytes);
-    return OTGAN_ERR_WORKSPACE;
-  }
+  if (int rc = check_workspace(workspace, workspace_bytes, need)) return rc;
   return launch_sinkhorn(K, P, n, m, iters, lambda, plan, planT, stats, (float*)workspace,
                          (hipStream_t)stream);
 }

@@ -66,6 +66,39 @@ def _stack(shards):
         return torch.cat([s.detach() for s in shards], 0).contiguous()
 
 
+def _flat_pair(fa, fb, shape):
+    """The flat feature arrays of a training-mode call, validated ("[2N, D]": an even row count), detached, contiguous."""
+    for t in (fa, fb):
+        if not t.is_cuda:
+            raise _lib.OtganError("matching needs CUDA (MI355X) tensors; there is no CPU fallback")
+        if t.dtype != torch.float32 or t.dim() != 2 or t.shape != fa.shape or (shape == "[2N, D]" and t.shape[0] % 2):
+            raise ValueError(f"fa and fb must be float32 {shape} tensors of one shape")
+    return fa.detach().contiguous(), fb.detach().contiguous()
+
+
+def _buffers(dev, nout, nrows, D, ws_bytes):
+    """What every matching call writes: `nout` [nrows, D] outputs, the entropy, the fp64 distance; and its workspace."""
+    outs = [torch.empty((nrows, D), dtype=torch.float32, device=dev) for _ in range(nout)]
+    entropy = torch.empty((), dtype=torch.float32, device=dev)
+    dist = torch.empty((), dtype=torch.float64, device=dev)
+    return outs, entropy, dist, _workspace(ws_bytes, dev)
+
+
+def _grad_buffers(dev, need_b, nrows, D, ws_bytes):
+    """_buffers of a training-mode call -> (grad_a, grad_b or None, entropy, dist, workspace)."""
+    outs, entropy, dist, ws = _buffers(dev, 2 if need_b else 1, nrows, D, ws_bytes)
+    return outs[0], (outs[1] if need_b else None), entropy, dist, ws
+
+
+def _log_kernels(log_kernels, P, n):
+    """Precomputed log-kernels as the library reads them: contiguous float32 [P, n, n] (None stays None)."""
+    if log_kernels is None:
+        return None
+    log_kernels = log_kernels.contiguous()
+    assert tuple(log_kernels.shape) == (P, n, n) and log_kernels.dtype == torch.float32
+    return log_kernels
+
+
 class MatchedFeatures(tuple):
     """The reference's 5-tuple, carrying a few extras as attributes (flat outputs, the
     device-side fp64 distance and per-problem statistics) so that calc_distance and the
@@ -79,14 +112,9 @@ def _run(mode, fa, fb, S, lam, iters, cost_kind):
     L = _lib.lib()
     rows_total, D = fa.shape
     rows = rows_total // 2 if mode == _MODE_TWO else rows_total
-    dev = fa.device
-    outs = [torch.empty_like(fa) for _ in range(4)]
-    entropy = torch.empty((), dtype=torch.float32, device=dev)
-    dist = torch.empty((), dtype=torch.float64, device=dev)
+    outs, entropy, dist, ws = _buffers(fa.device, 4, rows_total, D, L.otgan_matching_workspace_bytes(mode, rows, D))
     nprob = 6 if mode == _MODE_TWO else 3
-    stats = torch.empty((nprob, 4), dtype=torch.float64, device=dev)
-    need = L.otgan_matching_workspace_bytes(mode, rows, D)
-    ws = _workspace(need, dev)
+    stats = torch.empty((nprob, 4), dtype=torch.float64, device=fa.device)
     s = _lib.stream_ptr()
     if mode == _MODE_TWO:
         rc = L.otgan_matching_two_batch_f32(fa.data_ptr(), fb.data_ptr(), rows, D, D, float(lam),
@@ -178,16 +206,9 @@ def get_matched_features_rows(features_a, features_b, sinkhorn_lambda, nr_sinkho
     L = _lib.lib()
     rows_total, D = fa.shape
     N = rows_total // 2
-    dev = fa.device
-    if log_kernels is not None:
-        log_kernels = log_kernels.contiguous()
-        assert tuple(log_kernels.shape) == (6, N, N) and log_kernels.dtype == torch.float32
-    outs = [torch.empty((row_count, D), dtype=fa.dtype, device=dev) for _ in range(4)]
-    entropy = torch.empty((), dtype=torch.float32, device=dev)
-    dist = torch.empty((), dtype=torch.float64, device=dev)
-    stats = torch.empty((6, 4), dtype=torch.float64, device=dev)
-    need = L.otgan_matching_workspace_bytes(_MODE_TWO, N, D)
-    ws = _workspace(need, dev)
+    log_kernels = _log_kernels(log_kernels, 6, N)
+    outs, entropy, dist, ws = _buffers(fa.device, 4, row_count, D, L.otgan_matching_workspace_bytes(_MODE_TWO, N, D))
+    stats = torch.empty((6, 4), dtype=torch.float64, device=fa.device)
     rc = L.otgan_matching_two_batch_rows_f32(fa.data_ptr(), fb.data_ptr(), N, D, D, float(sinkhorn_lambda),
                                              int(nr_sinkhorn_iter), int(row_begin), int(row_count),
                                              _lib.ptr(log_kernels),
@@ -206,22 +227,12 @@ def matched_feature_grads(fa, fb, sinkhorn_lambda, nr_sinkhorn_iter, need_b=True
     row_count)`: only that row range (inside one mini-batch: the samples of one data-parallel rank), `log_kernels` as in
     get_matched_features_rows.  Returns (grad_a, grad_b or None, entropy, distance): [rows, D] float32 tensors, a 0-d
     float32 and a 0-d float64 tensor (closed form of calc_distance from the Sinkhorn statistics)."""
-    for t in (fa, fb):
-        if not t.is_cuda:
-            raise _lib.OtganError("matching needs CUDA (MI355X) tensors; there is no CPU fallback")
-        if t.dtype != torch.float32 or t.dim() != 2 or t.shape != fa.shape or t.shape[0] % 2:
-            raise ValueError("fa and fb must be float32 [2N, D] tensors of one shape")
-    fa, fb = fa.detach().contiguous(), fb.detach().contiguous()
+    fa, fb = _flat_pair(fa, fb, "[2N, D]")
     L = _lib.lib()
     rows_total, D = fa.shape
     N = rows_total // 2
-    dev = fa.device
     nrows = rows_total if rows is None else int(rows[1])
-    grad_a = torch.empty((nrows, D), dtype=fa.dtype, device=dev)
-    grad_b = torch.empty((nrows, D), dtype=fa.dtype, device=dev) if need_b else None
-    entropy = torch.empty((), dtype=torch.float32, device=dev)
-    dist = torch.empty((), dtype=torch.float64, device=dev)
-    ws = _workspace(L.otgan_matching_grad_workspace_bytes(N, D), dev)
+    grad_a, grad_b, entropy, dist, ws = _grad_buffers(fa.device, need_b, nrows, D, L.otgan_matching_grad_workspace_bytes(N, D))
     if rows is None:
         if log_kernels is not None:
             raise ValueError("log_kernels are only taken by the row-range variant")
@@ -231,9 +242,7 @@ def matched_feature_grads(fa, fb, sinkhorn_lambda, nr_sinkhorn_iter, need_b=True
                                                  _lib.stream_ptr())
         _lib.check(rc, "otgan_matching_two_batch_grad_f32")
     else:
-        if log_kernels is not None:
-            log_kernels = log_kernels.contiguous()
-            assert tuple(log_kernels.shape) == (6, N, N) and log_kernels.dtype == torch.float32
+        log_kernels = _log_kernels(log_kernels, 6, N)
         rc = L.otgan_matching_two_batch_rows_grad_f32(fa.data_ptr(), fb.data_ptr(), N, D, D, float(sinkhorn_lambda),
                                                       int(nr_sinkhorn_iter), int(rows[0]), int(rows[1]),
                                                       _lib.ptr(log_kernels), grad_a.data_ptr(), _lib.ptr(grad_b), D,
@@ -277,7 +286,7 @@ class FeatureStack:
     @staticmethod
     def rank_plan(row_begin, row_count, N, need_b):
         """-> (ranges to split, stack rows of the rank's generated / data samples) for the rank that owns rows
-        [row_begin, +row_count) of the [2N] global batch.  Stack rows: a1 0, b1 N, b2 2N, a2 3N, a1 4N, b1 5N."""
+        [row_begin, +row_count) of the [2N] global batch.  The stack's block order is kStackGrad in csrc/sinkhorn.hip."""
         half, r0 = divmod(int(row_begin), N)
         if half == 0:
             # g(a1) contracts over [N, 4N) = b1 b2 a2 (also the Y blocks of (a1,a2) (a1,b1) (a1,b2)); with the data-side gradient
@@ -310,17 +319,13 @@ class FeatureStack:
     def rows_grad(self, sinkhorn_lambda, nr_sinkhorn_iter, rows, log_kernels, need_b=True):
         """matched_feature_grads(..., rows=rows, log_kernels=log_kernels) reading this stack."""
         L = _lib.lib()
-        N, D, dev = self.N, self.D, self.buf.device
-        log_kernels = log_kernels.contiguous()
-        assert tuple(log_kernels.shape) == (6, N, N) and log_kernels.dtype == torch.float32
+        N, D = self.N, self.D
+        log_kernels = _log_kernels(log_kernels, 6, N)
         nrows = int(rows[1])
-        grad_a = torch.empty((nrows, D), dtype=torch.float32, device=dev)
-        grad_b = torch.empty((nrows, D), dtype=torch.float32, device=dev) if need_b else None
-        entropy = torch.empty((), dtype=torch.float32, device=dev)
-        dist = torch.empty((), dtype=torch.float64, device=dev)
-        ws = _workspace(L.otgan_matching_grad_workspace_bytes(N, D), dev)
+        grad_a, grad_b, entropy, dist, ws = _grad_buffers(self.buf.device, need_b, nrows, D,
+                                                          L.otgan_matching_grad_workspace_bytes(N, D))
         rc = L.otgan_matching_two_batch_rows_grad_stack_f32(self.buf.data_ptr(), N, D, float(sinkhorn_lambda),
-                                                            int(nr_sinkhorn_iter), int(rows[0]), nrows, log_kernels.data_ptr(),
+                                                            int(nr_sinkhorn_iter), int(rows[0]), nrows, _lib.ptr(log_kernels),
                                                             grad_a.data_ptr(), _lib.ptr(grad_b), D, entropy.data_ptr(),
                                                             dist.data_ptr(), None, ws.data_ptr(), ws.numel(), _lib.stream_ptr())
         _lib.check(rc, "otgan_matching_two_batch_rows_grad_stack_f32")
@@ -334,24 +339,13 @@ def matched_feature_grads_single_batch(fa, fb, sinkhorn_lambda, nr_sinkhorn_iter
     `rows=(row_begin, row_count)`: only the rows of one data-parallel rank; `log_kernels` [3, n, n]: the a-a, b-b (both with
     -lambda*999 on the diagonal) and a-b log-kernels, e.g. all-gathered row slices (utils/matching.py:99-104).  Returns
     (grad_a, grad_b or None, entropy, distance) like matched_feature_grads."""
-    for t in (fa, fb):
-        if not t.is_cuda:
-            raise _lib.OtganError("matching needs CUDA (MI355X) tensors; there is no CPU fallback")
-        if t.dtype != torch.float32 or t.dim() != 2 or t.shape != fa.shape:
-            raise ValueError("fa and fb must be float32 [n, D] tensors of one shape")
-    fa, fb = fa.detach().contiguous(), fb.detach().contiguous()
+    fa, fb = _flat_pair(fa, fb, "[n, D]")
     L = _lib.lib()
     n, D = fa.shape
-    dev = fa.device
     r0, cnt = (0, n) if rows is None else (int(rows[0]), int(rows[1]))
-    grad_a = torch.empty((cnt, D), dtype=fa.dtype, device=dev)
-    grad_b = torch.empty((cnt, D), dtype=fa.dtype, device=dev) if need_b else None
-    entropy = torch.empty((), dtype=torch.float32, device=dev)
-    dist = torch.empty((), dtype=torch.float64, device=dev)
-    ws = _workspace(L.otgan_matching_single_batch_grad_workspace_bytes(n, D), dev)
-    if log_kernels is not None:
-        log_kernels = log_kernels.contiguous()
-        assert tuple(log_kernels.shape) == (3, n, n) and log_kernels.dtype == torch.float32
+    grad_a, grad_b, entropy, dist, ws = _grad_buffers(fa.device, need_b, cnt, D,
+                                                      L.otgan_matching_single_batch_grad_workspace_bytes(n, D))
+    log_kernels = _log_kernels(log_kernels, 3, n)
     rc = L.otgan_matching_single_batch_rows_grad_f32(fa.data_ptr(), fb.data_ptr(), n, D, D, float(sinkhorn_lambda),
                                                      int(nr_sinkhorn_iter), r0, cnt, _lib.ptr(log_kernels),
                                                      grad_a.data_ptr(), _lib.ptr(grad_b), D, entropy.data_ptr(),

@@ -206,3 +206,71 @@ def test_grad_abi_errors(dev):
         matching.matched_feature_grads(fa.cpu(), fa.cpu(), 10.0, 5)
     with pytest.raises(ValueError):
         matching.matched_feature_grads(fa[:63], fa[:63], 10.0, 5)
+
+
+@pytest.mark.parametrize("N,D", [(32, 64),      # the fp32 engines, the one-workgroup Sinkhorn kernel
+                                 (256, 64)],    # the split-precision engine, the panel kernel
+                         ids=["N32", "N256"])
+def test_grad_entry_points_copy_their_statistics_out(dev, N, D):
+    """The four training-mode entry points with `stats != NULL` (every Python caller passes None): the [P, 4] fp64 statistics
+    {row-entropy sum, <M, C>, sum(M), failure} they copy out must be the ones their own results were formed from.
+      distance = the closed form evaluated here in fp64 -- two-batch (2 T0 + 2 T1 - T2 - T3 - T4 - T5) / (4 N), single-batch
+                 (T1 + T0 - 2 T2) / (2 n), T = stats[:, 2] - stats[:, 1] -- to 16 * 2^-53 * sum |c_p T_p| / denom: the device
+                 compiler's fused multiply-adds over a handful of fp64 operations, nothing else.  The single-batch kernel adds
+                 999 trace(M_aa), 999 trace(M_bb), exactly 0 at lambda = 500 (exp(-499 500 + potentials) underflows): asserted
+                 on the plans of the staged entry points (otgan_cost_matrix_f32 with 999 on the diagonal, then
+                 otgan_sinkhorn_plan_f32) -- get_matched_features_single_batch returns matched features and statistics, from
+                 which no diagonal can be read.
+      entropy  = float32(mean_p(stats[p, 0] / n)) to one fp32 ulp.
+      a rows call returns the statistics of the full call on the same input to 1e-12 relative (sums by fp64 atomics)."""
+    from otgan_amd import _lib
+    from otgan_amd.utils import matching
+    L = _lib.lib()
+    lam, iters = 500.0, 10
+    rng = np.random.RandomState(23)
+    unit = lambda x: (x / np.linalg.norm(x, axis=1, keepdims=True)).astype(np.float32)
+    fa, fb = _t(unit(rng.randn(2 * N, D)), dev), _t(unit(rng.randn(2 * N, D)), dev)
+    s = _lib.stream_ptr()
+
+    def call(single, rows):
+        n, P = (N, 3) if single else (N, 6)
+        a, b = (fa[:N].contiguous(), fb[:N].contiguous()) if single else (fa, fb)
+        cnt = rows[1] if rows else a.shape[0]
+        ga, gb = torch.empty((cnt, D), device=dev), torch.empty((cnt, D), device=dev)
+        ent = torch.empty((), dtype=torch.float32, device=dev)
+        dist = torch.empty((), dtype=torch.float64, device=dev)
+        stats = torch.full((P, 4), float("nan"), dtype=torch.float64, device=dev)
+        need = (L.otgan_matching_single_batch_grad_workspace_bytes if single else L.otgan_matching_grad_workspace_bytes)(n, D)
+        ws = torch.empty(int(need), dtype=torch.uint8, device=dev)
+        head = (a.data_ptr(), b.data_ptr(), n, D, D, lam, iters)
+        tail = (ga.data_ptr(), gb.data_ptr(), D, ent.data_ptr(), dist.data_ptr(), stats.data_ptr(), ws.data_ptr(), int(need), s)
+        name = "otgan_matching_%s_batch_%sgrad_f32" % ("single" if single else "two", "rows_" if rows else "")
+        mid = (int(rows[0]), int(rows[1]), None) if rows else ()
+        _lib.check(getattr(L, name)(*head, *mid, *tail), name)
+        st = stats.cpu().numpy()
+        T = st[:, 2] - st[:, 1]
+        c = np.array([1.0, 1.0, -2.0] if single else [2.0, 2.0, -1.0, -1.0, -1.0, -1.0])
+        denom = 2.0 * n if single else 4.0 * n
+        want = float(np.dot(c, T)) / denom
+        tol = 16 * 2.0 ** -53 * float(np.sum(np.abs(c * T))) / denom
+        print(name, "distance", float(dist), "closed form", want, "tol", tol, "entropy", float(ent))
+        assert np.all(st[:, 3] == 0.0), st
+        assert abs(float(dist) - want) <= tol, (name, float(dist), want, tol)
+        ent_want = np.float32(np.mean(st[:, 0] / n))
+        assert abs(np.float32(float(ent)) - ent_want) <= np.spacing(ent_want), (name, float(ent), ent_want)
+        return st
+
+    # the single-batch closed form holds only with no mass on the diagonals of the a-a and b-b plans
+    for x in (fa[:N].contiguous(), fb[:N].contiguous()):
+        K = matching.cost_log_kernel(x, x, lam, diag_add=999.0).contiguous()
+        plan, planT = torch.empty_like(K), torch.empty_like(K)
+        pst = torch.empty((1, 4), dtype=torch.float64, device=dev)
+        need = L.otgan_sinkhorn_workspace_bytes(1, N, N)
+        ws = torch.empty(int(need), dtype=torch.uint8, device=dev)
+        _lib.check(L.otgan_sinkhorn_plan_f32(K.data_ptr(), 1, N, N, iters, lam, plan.data_ptr(), planT.data_ptr(), pst.data_ptr(),
+                                             ws.data_ptr(), int(need), s), "otgan_sinkhorn_plan_f32")
+        assert float(plan.diagonal().abs().max()) == 0.0
+
+    for single, rows in ((False, (N + N // 2, N // 2)), (True, (N // 2, N // 2))):
+        full, part = call(single, None), call(single, rows)
+        assert np.all(np.abs(part[:, :3] - full[:, :3]) <= 1e-12 * np.abs(full[:, :3])), (single, part, full)
