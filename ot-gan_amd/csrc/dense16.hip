@@ -712,14 +712,14 @@ template <int PT, int WW>
 __global__ __launch_bounds__(256, 2) void dense16_fwd_h2_kernel(FwdH2Args a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smemh[];
   __shared__ float s_sc[2];
-  constexpr int NIT = PT + 1;
   constexpr int WBYTES = kH2SliceU16 * 2;                    // prepared weights of one slice: 20 steps x 1 KiB
   // the image width is a template parameter: tile rows, LDS row stride and plane size are then compile-time constants and the
   // plane / piece / tile offsets of the fragment reads fold into the ds_read immediates (one address add per tap pair
   // instead of one per read: 100 -> 10 per slice)
   constexpr bool W8 = WW == 8;
-  constexpr int TR = 64 * PT / WW, RS = WW == 8 ? 16 : WW + 2, LOGW = WW == 8 ? 3 : WW == 16 ? 4 : 5;
+  constexpr int TR = 64 * PT / WW, RS = WW == 8 ? 16 : WW + 2, LOGW = WW == 8 ? 3 : WW == 16 ? 4 : WW == 32 ? 5 : 6;
   constexpr int PLANE = (TR + 2) * RS * 32;                 // bytes of one (sign, piece) plane
+  constexpr int NIT = ((TR + 2) * WW * 4 + 255) / 256;      // staging passes: (TR + 2) x W pixels x 4 quads over 256 threads
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int p = lane & 15, g = lane >> 4;
   const int tiles_per_img = a.H / TR;
@@ -1165,14 +1165,14 @@ template <int PT, int WW>
 __global__ __launch_bounds__(256, 2) void dense16_bwd_h2_kernel(BwdH2Args a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smemh[];
   __shared__ float s_sc[2];
-  constexpr int NIT = PT + 1;
   constexpr int WBYTES = kH2SliceU16 * 2;
   // the image width is a template parameter: tile rows, LDS row stride and plane size are then compile-time constants and the
   // plane / piece / tile offsets of the fragment reads fold into the ds_read immediates (one address add per tap pair
   // instead of one per read: 100 -> 10 per slice)
   constexpr bool W8 = WW == 8;
-  constexpr int TR = 64 * PT / WW, RS = WW == 8 ? 16 : WW + 2, LOGW = WW == 8 ? 3 : WW == 16 ? 4 : 5;
+  constexpr int TR = 64 * PT / WW, RS = WW == 8 ? 16 : WW + 2, LOGW = WW == 8 ? 3 : WW == 16 ? 4 : WW == 32 ? 5 : 6;
   constexpr int PLANE = (TR + 2) * RS * 32;                 // bytes of one (sign, piece) plane
+  constexpr int NIT = ((TR + 2) * WW * 4 + 255) / 256;      // staging passes: (TR + 2) x W pixels x 4 quads over 256 threads
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int p = lane & 15, g = lane >> 4;
   const int tiles_per_img = a.H / TR;
@@ -2062,7 +2062,7 @@ static int h2_pt(int N, int H, int W) {
 size_t dense16_h2_filter_bytes(int nsl) { return nsl > 0 ? (size_t)kH2HdrBytes + (size_t)nsl * kH2SliceU16 * 2 : 0; }
 
 bool dense16_h2_shape_ok(int N, int H, int W) {
-  if (!(W == 8 || W == 16 || W == 32) || H * W < 64) return false;
+  if (!(W == 8 || W == 16 || W == 32 || W == 64) || H * W < 64) return false;
   const int PT = h2_pt(N, H, W);
   const int TR = 64 * PT / W;
   return TR >= 1 && H % TR == 0 && (W != 8 || PT == 1);   // (8-wide images: only the one-tile instantiation exists)
@@ -2090,7 +2090,22 @@ int dense16_fwd_h2(int N, int H, int W, int nsl, const float* x, int ldx, const 
   const bool w8 = W == 8;
 #define D16_H2(PT_, W_) hipLaunchKernelGGL((dense16_fwd_h2_kernel<PT_, W_>), grid, blk, lds, s, a)
   (void)w8;
-  if (W == 32) { if (PT == 4) D16_H2(4, 32); else if (PT == 2) D16_H2(2, 32); else D16_H2(1, 32); }
+  if (W == 64) {
+    if (PT == 4) {
+      // 69.5 KB of LDS (four planes of 6 x 66 pixels + the slice's weights): above the 64 KB default of dynamic shared memory;
+      // two workgroups per compute unit still fit the 160 KB, as at 32 x 32
+      static const bool once = [] {
+        return hipFuncSetAttribute(reinterpret_cast<const void*>(&dense16_fwd_h2_kernel<4, 64>), hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024) == hipSuccess;
+      }();
+      if (!once) {
+        otgan_set_error("dense16 fwd h2: the 64-wide four-row tile needs 69.5 KB of dynamic shared memory");
+        return OTGAN_ERR_UNSUPPORTED;
+      }
+      D16_H2(4, 64);
+    } else if (PT == 2) D16_H2(2, 64);
+    else D16_H2(1, 64);
+  }
+  else if (W == 32) { if (PT == 4) D16_H2(4, 32); else if (PT == 2) D16_H2(2, 32); else D16_H2(1, 32); }
   else if (W == 16) { if (PT == 4) D16_H2(4, 16); else if (PT == 2) D16_H2(2, 16); else D16_H2(1, 16); }
   else D16_H2(1, 8);
 #undef D16_H2
@@ -2165,7 +2180,8 @@ int dense16_bwd_h2(int N, int H, int W, int nsl, const float* g, int ldg, const 
   const bool w8 = W == 8;
 #define D16_B2(PT_, W_) hipLaunchKernelGGL((dense16_bwd_h2_kernel<PT_, W_>), grid, blk, lds, s, a)
   (void)w8;
-  if (W == 32) { if (PT == 4) D16_B2(4, 32); else if (PT == 2) D16_B2(2, 32); else D16_B2(1, 32); }
+  if (W == 64) { if (PT == 4) D16_B2(4, 64); else if (PT == 2) D16_B2(2, 64); else D16_B2(1, 64); }      // at most 44.75 KB of LDS
+  else if (W == 32) { if (PT == 4) D16_B2(4, 32); else if (PT == 2) D16_B2(2, 32); else D16_B2(1, 32); }
   else if (W == 16) { if (PT == 4) D16_B2(4, 16); else if (PT == 2) D16_B2(2, 16); else D16_B2(1, 16); }
   else D16_B2(1, 8);
 #undef D16_B2

@@ -275,6 +275,10 @@ _GLU_COLSUM = True        # the gate's backward kernel also leaves the column su
 _GLU_FUSED = True         # the Winograd output transform writes the gated product beside y
 _GRAD_INPLACE = True      # DenseBlockFunction.backward walks ONE gradient buffer
 DENSE_SPLIT = True        # dense blocks: block input and finished halves through wide Winograd convolutions (_split_block_plan)
+# growth chains of 64-pixel-wide blocks on the two-scaled-fp16-piece kernels (True) or on the fp32 / three-piece kernels (False).
+# Decided by an A/B of one whole block, forward + backward (128 images, C0 = 32, L = 16): h2 10.53 ms against 15.18 ms, medians
+# of 7 alternating runs, the old route's runs 0.05 ms apart (profiles/densenet64_growth_ab.txt)
+DENSE_H2_AT_64 = True
 DENSE_GROUP = None        # growth outputs per wide convolution; None = half the block
 DENSE_AMAX = True         # one record array per dense block, filled by the kernels that write its channels
 WN_BATCHED = True         # one weight-norm launch per dense block
@@ -951,7 +955,7 @@ def _split_block_plan(N, H, W, C0, L, F, segs0, preact, device):
     # the chains on the two-scaled-fp16-piece kernel (CReLU, 16-channel list elements; otgan_layers.h: list_width)
     probe = ConvDesc(N, H, W, F, Ctot, 0, 3, 3, 1, F, Ctot, C0, preact, 1)
     probe.y_accumulate, probe.list_width = 1, F
-    h2 = bool(lib.otgan_dense16_h2_ok(ctypes.byref(probe))) and DENSE_AMAX and _FUSED_AMAX
+    h2 = bool(lib.otgan_dense16_h2_ok(ctypes.byref(probe))) and DENSE_AMAX and _FUSED_AMAX and (W != 64 or DENSE_H2_AT_64)
     # the library prepares at most OTGAN_DENSE16_MAX_BATCH chain layers per call (forward and by-slice backward filters) and
     # a chain call takes at most 17 slices per group: longer blocks / groups (layers_per_block > 18 at the default grouping)
     # keep the fp32 growth kernels

@@ -9,7 +9,8 @@ matching problem (it must be even, train.py:34) -- and is decoupled from the num
 physical GPUs (= torch.distributed world size): every rank owns nr_gpu / world shards.
 
 Added flags (not in the reference): --synthetic (random CIFAR-shaped data instead of the
-pickled dataset), --synthetic_size, --matching_scope global|local, --max_steps, --image_size, --save_every,
+pickled dataset), --synthetic_size, --matching_scope global|local, --max_steps, --image_size (32 | 64, both models; the
+reference is 32 x 32 only), --save_every,
 --data_dependent_init, --eval_every / --eval_samples / --inception_model (the reference's Inception-score hook,
 train.py:245-272: --inception_model takes the reference's own 2015 graph file, or a TorchScript classifier),
 --fid_stats / --fid_real_samples (the Frechet Inception Distance beside every score, utils/fid.py).
@@ -50,10 +51,12 @@ def build_parser():
     p.add_argument('--model_name', type=str, default='med_gan_params-2399')
     p.add_argument('--no_sinkhorn', dest='no_sinkhorn', action='store_true')
     # ---- additions
-    p.add_argument('--synthetic', action='store_true', help='uniform random 32x32x3 data instead of CIFAR-10')
+    p.add_argument('--synthetic', action='store_true', help='uniform random image_size x image_size x 3 data instead of CIFAR-10')
     p.add_argument('--matching_scope', type=str, default='global', choices=['global', 'local'])
     p.add_argument('--max_steps', type=int, default=0, help='stop after this many steps (0 = run like the reference)')
-    p.add_argument('--image_size', type=int, default=32)
+    p.add_argument('--image_size', type=int, default=32,
+                   help='side of the generated / critic images: 32 (the reference) or 64 for --model dcgan and --model densenet; '
+                        '64 needs 64x64 data (--synthetic: the CIFAR-10 loader is 32x32)')
     p.add_argument('--save_every', type=int, default=200, help='checkpoint every this many epochs (reference: 200, train.py:275)')
     p.add_argument('--synthetic_size', type=int, default=50000, help='number of synthetic images with --synthetic')
     p.add_argument('--data_dependent_init', action='store_true',

@@ -63,7 +63,7 @@ _NO_REGION = _NoRegion()
 
 class OTGAN:
     """State of one training run.  `args` carries the reference's flags (train.py:14-33)
-    plus: image_size, matching_scope ('global' = one OT problem set over all ranks, the
+    plus: image_size (32 or 64, both models), matching_scope ('global' = one OT problem set over all ranks, the
     reference's semantics; 'local' = an independent problem set per rank)."""
 
     def __init__(self, args, device, init_batch=None):
@@ -96,8 +96,10 @@ class OTGAN:
         self.model_opts = {"nonlinearity": args.nonlinearity}
         size = getattr(args, "image_size", 32)
         if size != 32:
-            if args.model != "dcgan":
-                raise ValueError("--image_size other than 32 is only available for --model dcgan")
+            if args.model == "densenet":
+                mod.check_image_size(size)          # 32 or 64
+            elif args.model != "dcgan":
+                raise ValueError(f"--model {args.model} takes --image_size 32 only (dcgan and densenet also take 64)")
             self.model_opts["image_size"] = size
         # parameter creation pass (train.py:52-56; the data-dependent init it builds is never run by the reference:
         # default g = 1, b = 0; --data_dependent_init executes it on `init_batch`)
