@@ -461,4 +461,27 @@ int otgan_incep_head_f32(int N, int HW, int C, int ldx, int classes, const float
  */
 int otgan_moments_update_f64(int n, int C, int ldx, const float* x, double* sum, double* outer, void* stream);
 
+/*
+ * The training batch from a device-resident uint8 dataset in ONE launch (csrc/data.hip; utils/data.py): gather by the
+ * epoch's permutation, per-image horizontal flip, uint8 -> [-1, 1] and an optional integer box-downsample -- what the
+ * reference does on the host per step (train.py:158,163-170,209-211).
+ *   store: NHWC uint8 [n_images][SH][SW][3] (device, 4-byte aligned);  out: fp32 [n_shards * B][S][S][3] with row pitch
+ *   ldo >= 3 S S floats, ldo % 4 == 0, 16-byte aligned.  For output row r = s * B + k:
+ *     idx = perm ? perm[shard_offsets[s] + k] : shard_offsets[s] + k      (perm: device int32 [perm_len], nullable; its
+ *                                                                          VALUES are the caller's to validate: 0 <= . < n_images)
+ *     xs  = flip && flip[r] ? S - 1 - x : x                               (flip: device uint8 [n_shards * B], nullable)
+ *     f = SH / S = SW / S in {1, 2, 4}, S % 4 == 0
+ *     f == 1: out[r][y][x][c] = lut[store[idx][y][xs][c]]                 (lut: 256 device floats; the host passes
+ *             arange(256) / 127.5 - 1 in fp32, the expression of the host loader: the same bits by construction)
+ *     f > 1:  out[r][y][x][c] = (float)sum / (127.5f * f * f) - 1.0f, sum = the exact integer sum of the f x f box of channel
+ *             c at (f y, f xs)                                            (lut unused)
+ *   shard_offsets: HOST array of n_shards <= OTGAN_BATCH_U8_MAX_SHARDS entries (it travels in the kernel arguments); every
+ *   shard must lie inside the permutation (the store without one): shard_offsets[s] + B <= perm_len (n_images).
+ * All byte offsets are 64-bit.  Enqueues exactly one kernel on `stream`: no allocation, no copy, no synchronisation.
+ */
+#define OTGAN_BATCH_U8_MAX_SHARDS 32
+int otgan_batch_from_u8_f32(const uint8_t* store, long n_images, int SH, int SW, const int32_t* perm, long perm_len,
+                            const long* shard_offsets, int n_shards, int B, const uint8_t* flip, const float* lut, int S,
+                            float* out, long ldo, void* stream);
+
 #endif /* OTGAN_LAYERS_H */

@@ -1779,3 +1779,43 @@ def ema_update(shadow, p, decay):
     bump_weights_epoch(shadow)
     _lib.check(_lib.lib().otgan_ema_update_f32(shadow.data_ptr(), p.data_ptr(), p.numel(),
                                                float(decay), _lib.stream_ptr()), "ema_update")
+
+
+BATCH_U8_MAX_SHARDS = 32   # include/otgan_layers.h
+
+
+def batch_from_u8(store, offsets, B, S, lut, perm=None, flip=None, out=None):
+    """The step's float32 batch from a device-resident uint8 store in one launch (otgan_batch_from_u8_f32): store uint8
+    [n, SH, SW, 3]; row s * B + k of the result is image perm[offsets[s] + k] (offsets[s] + k without a permutation), flipped
+    horizontally where flip[s * B + k] (bool / uint8, optional), through the 256-entry table `lut` (SH == S) or box-downsampled by
+    SH / S in {2, 4}.  `out`: a float32 [len(offsets) * B, S, S, 3] tensor whose images are contiguous and whose row stride is the
+    pitch (a row slice of a wider buffer); allocated when None.  Geometry errors come back as OtganError from the library."""
+    if not (store.is_cuda and store.dtype == torch.uint8 and store.dim() == 4 and store.shape[3] == 3 and store.is_contiguous()):
+        raise _lib.OtganError("batch_from_u8 takes a contiguous CUDA (MI355X) uint8 [n, H, W, 3] store; there is no CPU fallback")
+    rows = len(offsets) * int(B)
+    if out is None:
+        out = torch.empty(rows, S, S, 3, dtype=torch.float32, device=store.device)
+    if not (out.dtype == torch.float32 and out.shape == (rows, S, S, 3) and out[:1].is_contiguous() and out.device == store.device):
+        raise _lib.OtganError("batch_from_u8: out must be float32 [%d, %d, %d, 3] on %s with contiguous images, found %s %s on %s"
+                              % (rows, S, S, store.device, out.dtype, tuple(out.shape), out.device))
+    if perm is not None and not (perm.dtype == torch.int32 and perm.dim() == 1 and perm.is_contiguous()
+                                 and perm.device == store.device):
+        raise _lib.OtganError("batch_from_u8: perm must be a contiguous 1-D int32 tensor on %s, found %s %s on %s"
+                              % (store.device, perm.dtype, tuple(perm.shape), perm.device))
+    if flip is not None:
+        if flip.dtype == torch.bool and flip.is_contiguous():
+            flip = flip.view(torch.uint8)      # a bool tensor stores one byte 0 / 1 per element
+        if not (flip.dtype == torch.uint8 and flip.numel() == rows and flip.is_contiguous() and flip.device == store.device):
+            raise _lib.OtganError("batch_from_u8: flip must be %d contiguous bool / uint8 values on %s, found %s %s on %s"
+                                  % (rows, store.device, flip.dtype, tuple(flip.shape), flip.device))
+    if not (lut.dtype == torch.float32 and lut.numel() == 256 and lut.is_contiguous() and lut.device == store.device):
+        raise _lib.OtganError("batch_from_u8: lut must be 256 contiguous float32 values on %s, found %s %s on %s"
+                              % (store.device, lut.dtype, tuple(lut.shape), lut.device))
+    off = (ctypes.c_long * len(offsets))(*[int(o) for o in offsets])
+    with torch.cuda.device(store.device):
+        _lib.check(_lib.lib().otgan_batch_from_u8_f32(store.data_ptr(), store.shape[0], store.shape[1], store.shape[2],
+                                                      _lib.ptr(perm), perm.numel() if perm is not None else 0,
+                                                      ctypes.cast(off, ctypes.c_void_p), len(offsets), int(B), _lib.ptr(flip),
+                                                      lut.data_ptr(), int(S), out.data_ptr(), out.stride(0) if rows > 1 else 3 * S * S,
+                                                      _lib.stream_ptr()), "batch_from_u8")
+    return out

@@ -13,7 +13,11 @@ pickled dataset), --synthetic_size, --matching_scope global|local, --max_steps, 
 reference is 32 x 32 only), --save_every,
 --data_dependent_init, --eval_every / --eval_samples / --inception_model (the reference's Inception-score hook,
 train.py:245-272: --inception_model takes the reference's own 2015 graph file, or a TorchScript classifier),
---fid_stats / --fid_real_samples (the Frechet Inception Distance beside every score, utils/fid.py).
+--fid_stats / --fid_real_samples (the Frechet Inception Distance beside every score, utils/fid.py),
+--dataset cifar10|imagenet64|npy and --data_on_device (utils/data.py): the training set lives on the device as uint8 and
+one kernel launch per step gathers, flips and converts the step's batch; 64 x 64 data (the downsampled-ImageNet pickles, a
+.npy of one's own images) comes in this way only.  Guarantee: `--dataset cifar10 --data_on_device` feeds `model.step` the
+same bits as the default host path, step for step (same host and device random streams, same conversion table).
 
 Checkpoints (`<save_dir>/med_gan_params-<epoch>`, the reference's naming, train.py:275-277) are torch pickles
 of {variable name: tensor} plus optimiser moments / step count and EMA shadows (which the reference's
@@ -56,7 +60,7 @@ def build_parser():
     p.add_argument('--max_steps', type=int, default=0, help='stop after this many steps (0 = run like the reference)')
     p.add_argument('--image_size', type=int, default=32,
                    help='side of the generated / critic images: 32 (the reference) or 64 for --model dcgan and --model densenet; '
-                        '64 needs 64x64 data (--synthetic: the CIFAR-10 loader is 32x32)')
+                        '64 needs data of 64, 128 or 256 pixels a side (--dataset imagenet64 | npy, or --synthetic: CIFAR-10 is 32x32)')
     p.add_argument('--save_every', type=int, default=200, help='checkpoint every this many epochs (reference: 200, train.py:275)')
     p.add_argument('--synthetic_size', type=int, default=50000, help='number of synthetic images with --synthetic')
     p.add_argument('--data_dependent_init', action='store_true',
@@ -82,7 +86,20 @@ def build_parser():
                    help='replay whole steps as hipGraphs after the first period (single-process runs; bit-identical to the '
                         'eager steps).  Default: on for --model densenet (launch-bound: replay 25.5 ms against 27.6 - 29.6 ms), '
                         'off for dcgan (8.60 against 8.52 - 8.56 ms); --step_graph / --step_graph 1 forces it on, --step_graph 0 off')
+    p.add_argument('--dataset', type=str, default='cifar10', choices=['cifar10', 'imagenet64', 'npy'],
+                   help='what --data_dir holds (utils/data.py): the CIFAR-10 python batches (the reference), the downsampled-ImageNet '
+                        "64x64 batches train_data_batch_1 ... 10 (pickles or .npz), or one .npy / .npz file of uint8 [n, H, W, 3] images; "
+                        'data whose side is 2x or 4x --image_size is box-downsampled on the device')
+    p.add_argument('--data_on_device', action='store_true',
+                   help='keep the training set on the device as uint8 and make every batch there in one launch (gather, flip, '
+                        'uint8 -> [-1, 1]) instead of the per-step host gather and copy; the same batches bit for bit.  Implied by '
+                        '--dataset imagenet64 | npy, which have no host-float path; with --synthetic: a random uint8 set')
     return p
+
+
+def uses_device_data(args):
+    """The device-resident uint8 path (utils/data.py)?  --data_on_device, or a dataset that has no host-float loader."""
+    return bool(args.data_on_device) or args.dataset != 'cifar10'
 
 
 def inception_hook(model, args, classifier, state, rank=0, world=1):
@@ -168,7 +185,10 @@ def real_fid_stats(args, classifier, trainx, rank=0, world=1):
         if rank == 0:
             print('FID statistics of the real data: loaded %s (%s)' % (args.fid_stats, '%d images' % n if n else 'n not recorded'))
         return mu, sigma
-    x = trainx[:args.fid_real_samples] if args.fid_real_samples else trainx
+    if not args.fid_real_samples:
+        x = trainx
+    else:       # (a utils.data.DeviceDataset has no slices: `head` shares its store)
+        x = trainx.head(args.fid_real_samples) if hasattr(trainx, "head") else trainx[:args.fid_real_samples]
     mu, sigma, n = fid.dataset_stats(classifier, x, rank, world)
     if rank == 0:
         fid.save_stats(args.fid_stats, mu, sigma, n)
@@ -249,11 +269,23 @@ def main(argv=None, self_launch=False):
         print(args)
     np.random.seed(args.seed)                                      # train.py:48
     torch.manual_seed(args.seed + rank)
-    if args.synthetic:
-        trainx = np.random.rand(args.synthetic_size, args.image_size, args.image_size, 3).astype(np.float32) * 2 - 1
+    on_device = uses_device_data(args)
+    if on_device:
+        # the set as uint8 on the device (every rank holds all of it); an --image_size the data cannot feed is a ValueError here
+        from .utils import data as udata
+        if args.synthetic:
+            u8 = np.random.randint(0, 256, (args.synthetic_size, args.image_size, args.image_size, 3), dtype=np.uint8)
+        else:
+            u8 = udata.load_u8(args.dataset, args.data_dir)
+        trainx = udata.DeviceDataset(u8, dev, args.image_size)
+        del u8
+        init_batch = trainx.rows(0, min(args.batch_size, trainx.shape[0])) if args.data_dependent_init else None
     else:
-        trainx = load_cifar(args.data_dir)
-    init_batch = torch.from_numpy(trainx[:args.batch_size]) if args.data_dependent_init else None
+        if args.synthetic:
+            trainx = np.random.rand(args.synthetic_size, args.image_size, args.image_size, 3).astype(np.float32) * 2 - 1
+        else:
+            trainx = load_cifar(args.data_dir)
+        init_batch = torch.from_numpy(trainx[:args.batch_size]) if args.data_dependent_init else None
     model = OTGAN(args, dev, init_batch=init_batch)
     if rank == 0:
         print("model has a hidden representation with %d features" % model.num_features)   # train.py:56
@@ -283,16 +315,24 @@ def main(argv=None, self_launch=False):
     for epoch in range(current_epoch, 1000000):
         begin = time.time()
         inds = np.random.permutation(trainx.shape[0])              # same seed on every rank
+        if on_device:
+            trainx.set_permutation(inds)
         dg, dd, ent = [], [], []
         for t in range(nr_batches):
             # shard s of this step reads rows (t + s*nr_batches)*B ... (train.py:209-211)
-            rows = []
-            for j in range(model.shards):
-                s = rank * model.shards + j
-                td = t + s * nr_batches
-                rows.append(inds[td * args.batch_size:(td + 1) * args.batch_size])
-            xb = torch.from_numpy(trainx[np.concatenate(rows)]).to(dev, non_blocking=True)
-            r = model.step(maybe_flip(xb))
+            if on_device:
+                # the draw of maybe_flip (same device stream position), applied inside the gather
+                flip = torch.rand(model.shards * args.batch_size, device=dev) < 0.5
+                offs = [(t + (rank * model.shards + j) * nr_batches) * args.batch_size for j in range(model.shards)]
+                r = model.step(trainx.batch(offs, args.batch_size, flip))
+            else:
+                rows = []
+                for j in range(model.shards):
+                    s = rank * model.shards + j
+                    td = t + s * nr_batches
+                    rows.append(inds[td * args.batch_size:(td + 1) * args.batch_size])
+                xb = torch.from_numpy(trainx[np.concatenate(rows)]).to(dev, non_blocking=True)
+                r = model.step(maybe_flip(xb))
             (dd if r["kind"] == "disc" else dg).append(r["distance"])
             ent.append(r["entropy"])
             total += 1

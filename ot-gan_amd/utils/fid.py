@@ -128,7 +128,8 @@ def load_stats(path, C):
 
 
 def dataset_stats(classifier, images, rank=0, world=1):
-    """(mu, sigma, n) of pool_3 over `images` -- numpy [N, H, W, 3] in [-1, 1], the form of train.py's `trainx`.
+    """(mu, sigma, n) of pool_3 over `images` -- numpy [N, H, W, 3] in [-1, 1], the form of train.py's `trainx`, or a
+    `utils.data.DeviceDataset`, read through its `rows` (the same floats, converted on the device).
     Rank r classifies the contiguous share [r * ceil(N / world), (r + 1) * ceil(N / world)) on its device in the
     classifier's batches; one all-reduce; every rank returns the same values."""
     import torch
@@ -138,7 +139,10 @@ def dataset_stats(classifier, images, rank=0, world=1):
     acc = MomentAccumulator(classifier.plan.pool3_channels, classifier.device)
     bs = classifier.batch_size
     for i in range(lo, hi, bs):
-        x = torch.from_numpy(np.ascontiguousarray(images[i:min(i + bs, hi)], np.float32)).to(classifier.device)
+        if hasattr(images, "rows"):
+            x = images.rows(i, min(i + bs, hi))
+        else:
+            x = torch.from_numpy(np.ascontiguousarray(images[i:min(i + bs, hi)], np.float32)).to(classifier.device)
         acc.update(classifier.run(x, 127.5, 127.5)[0])
     n, s, o = acc.all_reduce().moments()
     mu, sigma = stats_from_moments(n, s, o)
