@@ -198,13 +198,12 @@ def weightnorm_fwd(V2d, g):
     w = torch.empty_like(V2d)
     wT = torch.empty((Cout, K), dtype=V2d.dtype, device=V2d.device)
     inv = torch.empty(Cout, dtype=V2d.dtype, device=V2d.device)
-    rec = amax_slot(V2d.device) if _FUSED_AMAX else None
+    rec = amax_slot(V2d.device)
     _lib.check(_lib.lib().otgan_weightnorm_fwd_amax_f32(V2d.data_ptr(), g.data_ptr(), K, Cout,
-                                                        w.data_ptr(), wT.data_ptr(), inv.data_ptr(), _lib.ptr(rec),
+                                                        w.data_ptr(), wT.data_ptr(), inv.data_ptr(), rec.data_ptr(),
                                                         _lib.stream_ptr()), "weightnorm_fwd")
-    if rec is not None:
-        tag_amax(w, rec)
-        tag_amax(wT, rec)
+    tag_amax(w, rec)
+    tag_amax(wT, rec)
     return w, wT, inv
 
 
@@ -228,8 +227,37 @@ def colsum(a2d_ptr, rows, cols, lda, device):
     return out
 
 
-def conv_fwd_raw(desc, x, cmap, wT, bias, y, filters=None):
+# Per-launch fields of `otgan_conv_desc`: what ONE launch reads or writes beside its geometry (N ... list_quads, list_width).
+# A descriptor that is kept -- in a ctx, in a dense-block plan -- holds geometry only; every launcher works on a private copy
+# of the descriptor it is given, with the fields of its keyword arguments filled in.
+_LAUNCH_POINTERS = ("x_amax", "dy_amax", "w_amax", "y_amax_out", "dx_amax_out", "glu_out", "glu_amax_out", "x_operand")
+_LAUNCH_INTS = ("ldy", "y_accumulate")
+
+
+def launch_desc(desc, **fields):
+    """A private copy of `desc` with the given per-launch fields set: tensors (None: a null pointer) for the records, the
+    gated product and the kept operand, `(records, count)` for x_amax / dy_amax with consecutive records, integers for ldy
+    (the channel stride of dy in a backward launch) and y_accumulate.  Fields that are not named keep what `desc` holds.
+    A launch and the queries that decide about it (amax_fused, otgan_conv2d_glu_fused, filter / operand bytes) take the
+    same copy."""
+    d = ConvDesc.from_buffer_copy(desc)
+    for name, v in fields.items():
+        if name in _LAUNCH_INTS:
+            setattr(d, name, int(v))
+        elif name in _LAUNCH_POINTERS:
+            if isinstance(v, tuple):
+                v, count = v
+                assert name in ("x_amax", "dy_amax"), name      # the two that may be `count` consecutive records
+                setattr(d, name + "_count", int(count))
+            setattr(d, name, _lib.ptr(v))
+        else:
+            raise TypeError(f"{name} is not a per-launch field of otgan_conv_desc")
+    return d
+
+
+def conv_fwd_raw(desc, x, cmap, wT, bias, y, filters=None, **fields):
     L = _lib.lib()
+    desc = launch_desc(desc, **fields)
     need = L.otgan_conv2d_workspace_bytes(ctypes.byref(desc), 0)
     ws = workspace(need, x.device)
     _lib.check(L.otgan_conv2d_fwd_pf_f32(ctypes.byref(desc), x.data_ptr(), _lib.ptr(cmap),
@@ -237,8 +265,9 @@ def conv_fwd_raw(desc, x, cmap, wT, bias, y, filters=None):
                                          ws.data_ptr(), ws.numel(), _lib.stream_ptr()), "conv2d_fwd")
 
 
-def conv_dgrad_raw(desc, dy, w, x, inv, dx, lddx, accumulate, filters=None):
+def conv_dgrad_raw(desc, dy, w, x, inv, dx, lddx, accumulate, filters=None, **fields):
     L = _lib.lib()
+    desc = launch_desc(desc, **fields)
     need = L.otgan_conv2d_workspace_bytes(ctypes.byref(desc), 1)
     ws = workspace(need, dy.device)
     _lib.check(L.otgan_conv2d_dgrad_pf_f32(ctypes.byref(desc), dy.data_ptr(), w.data_ptr(), _lib.ptr(filters),
@@ -263,16 +292,12 @@ def absmax_record(t):
 # record used to come from one more pass over the tensor (absmax_record: 20 launches, 0.33 ms of a DCGAN step); now the
 # kernel that writes the tensor -- GLU forward / backward, the output transforms of the strided layers, the RGB-in
 # layer, the feature head's backward -- leaves it in a zeroed slot, and the tensor carries the slot to its consumer
-# as a Python attribute (checked against the tensor's version counter; a tensor that arrives without one, e.g.
-# through a view or from outside, is reduced as before).
+# (hand-offs, below; a tensor that arrives without one, e.g. through a view or from outside, is reduced as before).
 AMAX_RECORD_FLOATS = 512     # otgan_layers.h: OTGAN_AMAX_RECORD_FLOATS
 _AMAX_SLOTS = 256
 _amax_pool = {}       # device -> [zeroed [slots, AMAX_RECORD_FLOATS] tensor, next free slot]
-# Constants since round 6 (they were OTGAN_* environment switches while each mechanism was being A/B-ed; the measurements are in
+# Constants (they were OTGAN_* environment switches while each mechanism was being A/B-ed; the measurements are in
 # DESIGN / docs/history).  Tests that compare a mechanism with its predecessor patch the attribute in-process.
-_FUSED_AMAX = True        # producers leave the amax record of what they write
-_GLU_COLSUM = True        # the gate's backward kernel also leaves the column sums (bias gradient) of what it writes
-_GLU_FUSED = True         # the Winograd output transform writes the gated product beside y
 _GRAD_INPLACE = True      # DenseBlockFunction.backward walks ONE gradient buffer
 DENSE_SPLIT = True        # dense blocks: block input and finished halves through wide Winograd convolutions (_split_block_plan)
 # growth chains of 64-pixel-wide blocks on the two-scaled-fp16-piece kernels (True) or on the fp32 / three-piece kernels (False).
@@ -280,16 +305,51 @@ DENSE_SPLIT = True        # dense blocks: block input and finished halves throug
 # of 7 alternating runs, the old route's runs 0.05 ms apart (profiles/densenet64_growth_ab.txt)
 DENSE_H2_AT_64 = True
 DENSE_GROUP = None        # growth outputs per wide convolution; None = half the block
-DENSE_AMAX = True         # one record array per dense block, filled by the kernels that write its channels
-WN_BATCHED = True         # one weight-norm launch per dense block
+
+
+# ---- hand-offs: values that ride on a tensor from the autograd node that produced it to the one that consumes it ------
+# One attribute, (version, {kind: value}): the amax record ("amax"), the column sums ("colsum", GluFunction.backward -> the
+# bias gradient of the convolution in front) and the gated product ("glu", Conv2dFunction.forward with glu_hint ->
+# GluFunction.forward) of the tensor as it stood at that version.  The rule, stated once:
+#   * the stamp catches what torch writes: any in-place op bumps the counter and everything left on the tensor is stale;
+#   * the library writes through raw pointers, which the counter does not see: code that lets it write into a tensor it did
+#     not allocate calls forget() (DenseBlockFunction.backward, when it walks the incoming gradient in place);
+#   * a view shares its base's counter but not its attribute: a value does not follow a view (carry_amax does that), and an
+#     in-place write to the base or to a sibling view makes it stale -- read before you write (ExtendChannelsFunction).
+_HANDOFF = "_otgan_handoff"
+
+
+def leave(t, kind, value):
+    """Leave `value` on `t` for its consumer, valid while `t` stays at its current version.  Kinds left at the same
+    version stay; what was left at an older one is discarded."""
+    tag = getattr(t, _HANDOFF, None)
+    if tag is None or tag[0] != t._version:
+        tag = (t._version, {})
+        setattr(t, _HANDOFF, tag)
+    tag[1][kind] = value
+    return t
+
+
+def take(t, kind, remove=False):
+    """What leave() left on `t` under `kind`, or None: nothing there, or the tensor was modified since."""
+    tag = getattr(t, _HANDOFF, None)
+    if tag is None:
+        return None
+    if tag[0] != t._version:
+        delattr(t, _HANDOFF)         # stale: nobody can use it any more
+        return None
+    return tag[1].pop(kind, None) if remove else tag[1].get(kind)
+
+
+def forget(t):
+    """Drop everything left on `t` (a raw-pointer write is about to change it, or has)."""
+    if hasattr(t, _HANDOFF):
+        delattr(t, _HANDOFF)
 
 
 def colsum_of(t):
     """Column sums of `t` left by its producer (GluFunction.backward), or None."""
-    tag = getattr(t, "_otgan_colsum", None)
-    if tag is None or tag[1] != t._version:
-        return None
-    return tag[0]
+    return take(t, "colsum")
 
 
 def amax_slot(device):
@@ -334,16 +394,12 @@ def reset_amax_pool():
 
 def tag_amax(t, rec):
     """`t` was just written by a kernel that max-accumulated |t| into rec[0]."""
-    t._otgan_amax = (rec, t._version)
-    return t
+    return leave(t, "amax", rec)
 
 
 def amax_of(t):
     """The producer's amax record of `t`, or None (no record, or the tensor was modified since)."""
-    tag = getattr(t, "_otgan_amax", None)
-    if tag is None or tag[1] != t._version:
-        return None
-    return tag[0]
+    return take(t, "amax")
 
 
 def carry_amax(dst, src):
@@ -355,13 +411,13 @@ def carry_amax(dst, src):
 
 
 def amax_fused(desc, which):
-    return _FUSED_AMAX and bool(_lib.lib().otgan_conv2d_amax_fused(ctypes.byref(desc), which))
+    return bool(_lib.lib().otgan_conv2d_amax_fused(ctypes.byref(desc), which))
 
 
 def shared_x_operand(desc, device):
     """Buffer for `otgan_conv_desc::x_operand` (the forward pass leaves its transformed input there, the weight
     gradient of the same x reads it back instead of transforming x again), or None when the layer's two passes do not
-    share an operand.  Sets the descriptor field."""
+    share an operand.  Sets the field of the descriptor it is given: a launch_desc() copy, not one that is kept."""
     nbytes = _lib.lib().otgan_conv2d_operand_bytes(ctypes.byref(desc))
     if not nbytes:
         return None
@@ -370,24 +426,25 @@ def shared_x_operand(desc, device):
     return buf
 
 
-def prepare_filters(desc, which, w):
+def prepare_filters(desc, which, w, **fields):
     """Winograd-domain filters of a layer's forward (which=0, from wT) or dgrad (which=1, from w) pass, or None
-    when the pass does not run as a Winograd GEMM (otgan_layers.h)."""
+    when the pass does not run as a Winograd GEMM (otgan_layers.h).  w_amax is the record `w` carries unless given."""
     L = _lib.lib()
+    # left by weightnorm_fwd on the un-folded w / wT (folded weights are another tensor: no record, the kernel reduces them)
+    fields.setdefault("w_amax", amax_of(w))
+    desc = launch_desc(desc, **fields)
     nbytes = L.otgan_conv2d_filter_bytes(ctypes.byref(desc), which)
     if not nbytes:
         return None
     buf = torch.empty((nbytes + 3) // 4, dtype=torch.float32, device=w.device)
-    rec = amax_of(w)            # left by weightnorm_fwd on the un-folded w / wT (folded weights are another tensor)
-    desc.w_amax = rec.data_ptr() if rec is not None else None
     _lib.check(L.otgan_conv2d_prepare_filters_f32(ctypes.byref(desc), which, w.data_ptr(), buf.data_ptr(),
                                                   buf.numel() * 4, _lib.stream_ptr()), "prepare_filters")
-    desc.w_amax = None
     return buf
 
 
-def conv_wgrad_raw(desc, x, cmap, dy, dw):
+def conv_wgrad_raw(desc, x, cmap, dy, dw, **fields):
     L = _lib.lib()
+    desc = launch_desc(desc, **fields)
     need = L.otgan_conv2d_workspace_bytes(ctypes.byref(desc), 2)
     ws = workspace(need, dy.device)
     _lib.check(L.otgan_conv2d_wgrad_f32(ctypes.byref(desc), x.data_ptr(), _lib.ptr(cmap),
@@ -433,8 +490,8 @@ def join_side_stream(tensors=()):
             t.record_stream(cur)
 
 
-# The gated product a convolution wrote for the glu() that follows it (glu_hint) rides on the convolution's output as an
-# attribute until GluFunction.forward claims it.  A caller that passes the hint and then never applies glu to that very
+# The gated product a convolution wrote for the glu() that follows it (glu_hint) rides on the convolution's output (the
+# "glu" hand-off) until GluFunction.forward claims it.  A caller that passes the hint and then never applies glu to that very
 # tensor would keep the product alive as long as the output: the next convolution's forward pass drops it.
 _PENDING_GLU = [None]
 
@@ -443,8 +500,8 @@ def _drop_unclaimed_glu():
     ref = _PENDING_GLU[0]
     if ref is not None:
         t = ref()
-        if t is not None and hasattr(t, "_otgan_glu"):
-            del t._otgan_glu
+        if t is not None:
+            take(t, "glu", remove=True)
         _PENDING_GLU[0] = None
 
 
@@ -519,9 +576,9 @@ class Conv2dFunction(torch.autograd.Function):
                                       "bwd_done": False, "bwd_which": 3 if unf_b else 1}
 
         wd, wT, inv_norm, filt = cached_weights(V, g, compute)
-        w_rec = amax_of(wT)              # left by the weight-norm kernel (same values in w and wT); the implicit-GEMM passes'
-        ctx.w_rec = w_rec                # two-piece fp16 loop scales the weights by it (else it reduces them itself)
-        desc.w_amax = w_rec.data_ptr() if w_rec is not None else None
+        # left by the weight-norm kernel (same values in w and wT); the implicit-GEMM passes' two-piece fp16 loop scales the
+        # weights by it (else it reduces them itself)
+        ctx.w_rec = amax_of(wT)
         ctx.x_rec = None
         if filt["fwd"] is not None and x.is_contiguous() and C % 4 == 0:
             # Winograd passes: the record x's producer left (else one reduction of x), for the forward pass now and
@@ -529,35 +586,26 @@ class Conv2dFunction(torch.autograd.Function):
             ctx.x_rec = amax_of(x)
             if ctx.x_rec is None:
                 ctx.x_rec = absmax_record(x)
-            desc.x_amax = ctx.x_rec.data_ptr()
+        # the forward launch: the weights' record and the record of x -- the Winograd passes' own, else what x's producer
+        # left (the implicit-GEMM passes scale their two-piece operands by it, else they reduce x; the backward launches
+        # do not get that one)
+        fwd = launch_desc(desc, w_amax=ctx.w_rec, x_amax=ctx.x_rec if ctx.x_rec is not None else amax_of(x))
         # 288 GB of HBM: keep the transformed input of the Winograd passes for the weight gradient (0.15-0.6 GB a layer)
         ctx.x_op = None
         if (ctx.needs_input_grad[1] or ctx.needs_input_grad[2]) and cmap is None and filt["fwd"] is not None:
-            ctx.x_op = shared_x_operand(desc, x.device)
-        if ctx.x_rec is None:
-            x_tag = amax_of(x)               # implicit-GEMM passes scale their two-piece operands by it (else they reduce x)
-            desc.x_amax = x_tag.data_ptr() if x_tag is not None else None
-        y_rec = None
-        if amax_fused(desc, 0):
+            ctx.x_op = shared_x_operand(fwd, x.device)
+        y_rec = y_glu = glu_rec = None
+        if amax_fused(fwd, 0):
             y_rec = amax_slot(x.device)          # the kernel that writes y also leaves max |y| (for the next layer)
-            desc.y_amax_out = y_rec.data_ptr()
-        y_glu = None
-        if glu_hint and _GLU_FUSED and cmap is None and _lib.lib().otgan_conv2d_glu_fused(ctypes.byref(desc)):
+        if glu_hint and cmap is None and _lib.lib().otgan_conv2d_glu_fused(ctypes.byref(fwd)):
             # the caller applies a gated linear unit to y next (models/dcgan.py:50): the kernel that writes y leaves the
             # gated product (and its amax record) too; GluFunction.forward picks it up instead of reading y again
             y_glu = torch.empty((N, OH, OW, Cout // 2), dtype=x.dtype, device=x.device)
-            glu_rec = amax_slot(x.device) if _FUSED_AMAX else None
-            desc.glu_out, desc.glu_amax_out = y_glu.data_ptr(), _lib.ptr(glu_rec)
-        conv_fwd_raw(desc, x, cmap, wT, b, y, filt["fwd"])
+            glu_rec = amax_slot(x.device)
+        conv_fwd_raw(fwd, x, cmap, wT, b, y, filt["fwd"], y_amax_out=y_rec, glu_out=y_glu, glu_amax_out=glu_rec)
         if y_glu is not None:
-            desc.glu_out = desc.glu_amax_out = None
-            if glu_rec is not None:
-                tag_amax(y_glu, glu_rec)
-            y._otgan_glu = (y_glu, y._version)
+            leave(y, "glu", tag_amax(y_glu, glu_rec))
             _PENDING_GLU[0] = weakref.ref(y)
-        desc.y_amax_out = None
-        if ctx.x_rec is None:
-            desc.x_amax = None
         if y_rec is not None:
             tag_amax(y, y_rec)
         if (SIDE_STREAM is not None and ctx.needs_input_grad[0] and not filt["bwd_done"] and
@@ -570,7 +618,6 @@ class Conv2dFunction(torch.autograd.Function):
                 filt["bwd"], filt["bwd_done"] = prepare_filters(desc, filt["bwd_which"], wd), True
                 filt["bwd_event"] = SIDE_STREAM.record_event()
             wd.record_stream(SIDE_STREAM)
-            desc.w_amax = w_rec.data_ptr() if w_rec is not None else None      # (prepare_filters cleared it)
         ctx.save_for_backward(x, V2d, g, wd, inv_norm)
         ctx.filt = filt
         ctx.desc, ctx.cmap, ctx.inv = desc, cmap, inv
@@ -581,26 +628,12 @@ class Conv2dFunction(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dy):
         x, V2d, g, w, inv_norm = ctx.saved_tensors
-        desc = ctx.desc
         # dy may be the channel prefix of a dense block's gradient buffer (DenseBlockFunction.backward hands it on without a
         # copy): read in place through the ABI's channel stride.  Anything else is made contiguous.
-        ld_fwd = desc.ldy
         ld = channel_prefix_stride(dy)
         if ld is None:
-            rec = amax_of(dy)
-            dy = dy.contiguous()
+            dy = carry_amax(dy.contiguous(), dy)
             ld = dy.shape[-1]
-            if rec is not None:
-                tag_amax(dy, rec)
-        desc.ldy = ld
-        try:
-            return Conv2dFunction._backward_impl(ctx, dy, ld, x, V2d, g, w, inv_norm)
-        finally:
-            desc.ldy = ld_fwd
-
-    @staticmethod
-    def _backward_impl(ctx, dy, ld, x, V2d, g, w, inv_norm):
-        desc = ctx.desc
         dx = dV = dg = db = None
         dy_rec = None
         if ctx.x_rec is not None and dy.shape[-1] % 4 == 0:
@@ -608,7 +641,9 @@ class Conv2dFunction(torch.autograd.Function):
             if dy_rec is None:
                 dy_rec = (absmax_record(dy) if dy.is_contiguous() else
                           absmax_record_strided(dy.data_ptr(), dy.numel() // dy.shape[-1], dy.shape[-1], ld, dy.device))
-            desc.dy_amax = dy_rec.data_ptr()
+        # what every launch of this pass sees: dy's channel stride in place of y's, and the records / kept operand of the
+        # forward pass again
+        desc = launch_desc(ctx.desc, ldy=ld, w_amax=ctx.w_rec, x_amax=ctx.x_rec, x_operand=ctx.x_op, dy_amax=dy_rec)
         if ctx.needs_input_grad[0]:
             dx = torch.empty_like(x)
             filt = ctx.filt
@@ -625,10 +660,7 @@ class Conv2dFunction(torch.autograd.Function):
             # once whatever the channel map, round 4)
             if amax_fused(desc, 1) and (ctx.inv is None or filt["bwd"] is None):
                 dx_rec = amax_slot(x.device)
-                desc.dx_amax_out = dx_rec.data_ptr()
-            desc.w_amax = ctx.w_rec.data_ptr() if ctx.w_rec is not None else None    # (prepare_filters cleared it)
-            conv_dgrad_raw(desc, dy, w, x, ctx.inv, dx, x.shape[3], False, filt["bwd"])
-            desc.dx_amax_out = None
+            conv_dgrad_raw(desc, dy, w, x, ctx.inv, dx, x.shape[3], False, filt["bwd"], dx_amax_out=dx_rec)
             if dx_rec is not None:
                 tag_amax(dx, dx_rec)
         need_w = ctx.needs_input_grad[1] or ctx.needs_input_grad[2]
@@ -836,12 +868,11 @@ def _wide_operands(per_layer, layers, row0, nrows, order, F, desc):
         segs_t.append((wT_k.data_ptr(), wT.data_ptr() + 4 * j * F * 9 * nrows, F * 9, ceff, 1, nrows, 1))
     # the first gather also leaves the amax record of the gathered weights (w and wT hold the same elements): the filter
     # transforms of the wide convolution take it from there instead of reducing the weights again (15 launches per DenseNet step)
-    rec = amax_slot(ref.device) if _FUSED_AMAX else None
+    rec = amax_slot(ref.device)
     gather3d_batched(segs_w, nrows, F, row0, map32, rec)
     gather3d_batched(segs_t, nrows, 1, row0, map32)
-    if rec is not None:
-        tag_amax(w, rec)
-        tag_amax(wT, rec)
+    tag_amax(w, rec)
+    tag_amax(wT, rec)
     return {"w": w, "wT": wT, "fwd": prepare_filters(desc, 0, wT), "bwd": None, "bwd_done": False}
 
 
@@ -954,8 +985,8 @@ def _split_block_plan(N, H, W, C0, L, F, segs0, preact, device):
         wd["back"] = _row_order_back(wd["order"])
     # the chains on the two-scaled-fp16-piece kernel (CReLU, 16-channel list elements; otgan_layers.h: list_width)
     probe = ConvDesc(N, H, W, F, Ctot, 0, 3, 3, 1, F, Ctot, C0, preact, 1)
-    probe.y_accumulate, probe.list_width = 1, F
-    h2 = bool(lib.otgan_dense16_h2_ok(ctypes.byref(probe))) and DENSE_AMAX and _FUSED_AMAX and (W != 64 or DENSE_H2_AT_64)
+    probe.list_width = F
+    h2 = bool(lib.otgan_dense16_h2_ok(ctypes.byref(launch_desc(probe, y_accumulate=1)))) and (W != 64 or DENSE_H2_AT_64)
     # the library prepares at most OTGAN_DENSE16_MAX_BATCH chain layers per call (forward and by-slice backward filters) and
     # a chain call takes at most 17 slices per group: longer blocks / groups (layers_per_block > 18 at the default grouping)
     # keep the fp32 growth kernels
@@ -1012,8 +1043,8 @@ class DenseBlockFunction(torch.autograd.Function):
     only adds the convolution of the growth outputs of its own group (`y_accumulate`).  Backward mirrors it: the
     growth layers' dgrad / wgrad see their own group only, each wide convolution takes one dgrad and one wgrad
     against the finished gradient of the channels it wrote.  Same sums in a different order; chosen when the
-    library routes the wide convolutions to its Winograd path (OTGAN_DENSE_SPLIT=0: never, OTGAN_DENSE_GROUP=n:
-    groups of n, 0: the block input only).
+    library routes the wide convolutions to its Winograd path (the module constants DENSE_SPLIT = False: never,
+    DENSE_GROUP = n: groups of n, 0: the block input only).
 
     args: x0 [N,H,W,C0] (concatenated initial list), then V_k, g_k, b_k for every layer."""
 
@@ -1037,7 +1068,7 @@ class DenseBlockFunction(torch.autograd.Function):
             assert tuple(V.shape) == (ksize, ksize, (C0 + k * F) * mult, F), (V.shape, C0 + k * F, mult)
             V2ds.append(V.contiguous().view(-1, F))
         gs = list(params[1::3])
-        ctx.batched = F == 16 and ksize == 3 and _aligned16(*V2ds, *gs) and WN_BATCHED
+        ctx.batched = F == 16 and ksize == 3 and _aligned16(*V2ds, *gs)     # one weight-norm launch per block and pass
         batch = []
 
         def normalised(k):
@@ -1067,13 +1098,14 @@ class DenseBlockFunction(torch.autograd.Function):
                 sw["bias_all"], sw["bias_key"] = torch.cat([b.detach() for b in params[2::3]]), bkey
             bias_all = sw["bias_all"]
             rows = N * H * W
-            ctx.x_recs, ctx.x_ops = [], []
-            # amax records without extra passes (DENSE_AMAX False: one reduction per slice, as in round 2): every kernel
-            # that writes growth channels -- the wide convolutions (the second one adds onto the first) and the 16-output
-            # kernels of the chains -- leaves the largest magnitude of the values it writes in a record (layout below);
-            # the block's output carries max(record of x0, all of them) for the transition that reads the whole buffer.
-            shared = DENSE_AMAX and _FUSED_AMAX
-            rec_x0 = amax_of(x0) if shared else None
+            wides = plan["wide"]
+            # what the wide convolutions' backward launches get again: the record(s) of their input, their kept operand
+            ctx.x_recs, ctx.x_ops = [None] * len(wides), [None] * len(wides)
+            # amax records without extra passes: every kernel that writes growth channels -- the wide convolutions (the
+            # second one adds onto the first) and the 16-output kernels of the chains -- leaves the largest magnitude of the
+            # values it writes in a record (layout below); the block's output carries max(record of x0, all of them) for
+            # the transition that reads the whole buffer.
+            rec_x0 = amax_of(x0)
             # round 4: ONE zeroed array of records per block.  Group i (the layers between two wide convolutions) owns
             # rows [gbase(i), gbase(i + 1)): first the record of the sums the group's wide convolution leaves in the
             # growth channels it writes (W_i: bounds every slice a layer of the group finishes without a chain kernel,
@@ -1081,37 +1113,34 @@ class DenseBlockFunction(torch.autograd.Function):
             # that finishes the layer's slice.  A chain kernel reads rows [gbase, gbase + 1 + j) -- consecutive records,
             # otgan_conv_desc::x_amax_count -- as the bound of the slices it multiplies (the two-scaled-fp16-piece
             # kernel needs it; records are only ever read by launches after their writers: deterministic).
-            wides = plan["wide"]
             gbase = [wd["d0"] + i for i, wd in enumerate(wides)] + [L + len(wides)]
             gidx = {wd["d0"]: i for i, wd in enumerate(wides)}
-            R = amax_slots(buf.device, L + len(wides)) if shared else None
+            R = amax_slots(buf.device, L + len(wides))
 
             def wide_fwd(i):
-                wd, ops_ = plan["wide"][i], sw["wide"][i]
-                desc = wd["desc"]
+                wd, ops_ = wides[i], sw["wide"][i]
                 src = buf[..., wd["x_off"]:]       # channel slice: same rows, pointer advanced by x_off floats
-                nrec = 1
-                if shared and i == 0 and rec_x0 is not None:
-                    rec = rec_x0
-                elif shared and i > 0:
+                if i == 0 and rec_x0 is not None:
+                    x_amax = (rec_x0, 1)
+                elif i > 0:
                     # the finished slices of the group that feeds this convolution: its rows of R as they are
                     # (otgan_conv_desc::x_amax_count consecutive records; until round 4 an amax over them: one launch)
-                    rec, nrec = R[gbase[i - 1]:gbase[i]], gbase[i] - gbase[i - 1]
+                    x_amax = (R[gbase[i - 1]:gbase[i]], gbase[i] - gbase[i - 1])
                 else:
-                    rec = absmax_record_strided(src.data_ptr(), rows, wd["C"], Ctot, buf.device)
-                ctx.x_recs.append((rec, nrec))
-                desc.x_amax, desc.x_amax_count = rec.data_ptr(), nrec
+                    x_amax = (absmax_record_strided(src.data_ptr(), rows, wd["C"], Ctot, buf.device), 1)
+                ctx.x_recs[i] = x_amax
+                desc = launch_desc(wd["desc"], x_amax=x_amax, y_accumulate=wd["accumulate"], y_amax_out=R[gbase[i]])
                 if any(ctx.needs_input_grad[4:]):
-                    ctx.x_ops.append(shared_x_operand(desc, buf.device))    # read back by this convolution's wgrad
-                desc.y_accumulate = wd["accumulate"]
-                desc.y_amax_out = R[gbase[i]].data_ptr() if shared else None
+                    ctx.x_ops[i] = shared_x_operand(desc, buf.device)    # read back by this convolution's wgrad
                 conv_fwd_raw(desc, src, None, ops_["wT"], None if wd["accumulate"] else bias_all, buf, ops_["fwd"])
-                desc.y_accumulate = 0
-                desc.y_amax_out = None
-                desc.x_amax_count = 0
+
+            def chain_desc(n_own, k):
+                desc = ConvDesc(N, H, W, n_own * F, Ctot, 0, ksize, ksize, 1, F, Ctot, C0 + k * F, preact, 1)
+                desc.list_width = F
+                return desc
 
             wide_fwd(0)
-            chain_h2 = shared and plan.get("h2") and all(sw["h2"][k] is not None for k in range(L) if plan["own_len"][k])
+            chain_h2 = plan.get("h2") and all(sw["h2"][k] is not None for k in range(L) if plan["own_len"][k])
             if chain_h2:
                 # every group's chain in one library call (otgan_dense16_chain_fwd_f32: its layers' launches back to back)
                 lib = _lib.lib()
@@ -1126,45 +1155,29 @@ class DenseBlockFunction(torch.autograd.Function):
                                                                    _lib.stream_ptr()), "dense16_chain_fwd")
                 for k in range(L):      # descriptors / maps of the chain layers (their weight gradients use them)
                     n_own = plan["own_len"][k]
-                    if n_own:
-                        desc = ConvDesc(N, H, W, n_own * F, Ctot, 0, ksize, ksize, 1, F, Ctot, C0 + k * F, preact, 1)
-                        desc.list_width = F
-                        descs.append(desc)
-                        maps.append(channel_maps((F,) * n_own, preact, x0.device))
-                    else:
-                        descs.append(None)
-                        maps.append((None, None))
+                    descs.append(chain_desc(n_own, k) if n_own else None)
+                    maps.append(channel_maps((F,) * n_own, preact, x0.device) if n_own else (None, None))
             for k in range(L) if not chain_h2 else ():
                 n_own = plan["own_len"][k]
                 desc = cmap = inv = None
                 if n_own:
                     g0 = plan["g0"][k]
-                    desc = ConvDesc(N, H, W, n_own * F, Ctot, 0, ksize, ksize, 1, F, Ctot, C0 + k * F, preact, 1)
-                    desc.y_accumulate = 1
-                    desc.list_width = F
-                    if shared:
-                        gi = gidx[g0]
-                        desc.x_amax = R[gbase[gi]].data_ptr()
-                        desc.x_amax_count = 1 + n_own
-                        desc.y_amax_out = R[gbase[gi] + 1 + n_own].data_ptr()
+                    gi = gidx[g0]
+                    desc = chain_desc(n_own, k)
                     cmap, inv = channel_maps((F,) * n_own, preact, x0.device)
-                    conv_fwd_raw(desc, buf[..., C0 + g0 * F:], cmap, sw["wT_g"][k], None, buf, sw["h2"][k] if shared else None)
-                    desc.y_accumulate = 0
-                    desc.y_amax_out = None
-                    desc.x_amax = None
-                    desc.x_amax_count = 0
+                    conv_fwd_raw(desc, buf[..., C0 + g0 * F:], cmap, sw["wT_g"][k], None, buf, sw["h2"][k], y_accumulate=1,
+                                 x_amax=(R[gbase[gi]], 1 + n_own), y_amax_out=R[gbase[gi] + 1 + n_own])
                 descs.append(desc)
                 maps.append((cmap, inv))
-                for i, wd in enumerate(plan["wide"]):
+                for i, wd in enumerate(wides):
                     if wd["after"] == k:       # the group that ends with layer k is finished
                         wide_fwd(i)
             ctx.sw = sw
             ctx.save_for_backward(buf, *saved)
             ctx.descs, ctx.maps = descs, maps
-            ctx.fwd_recs = (R, gbase, gidx) if shared else None      # read again by the chains' weight gradients
-            if shared:
-                x0_rec = ctx.x_recs[0][0]     # the producer's record of x0, or the reduction wide_fwd(0) made
-                tag_amax(buf, torch.maximum(x0_rec, R.amax(0)))
+            ctx.fwd_recs = (R, gbase, gidx)      # read again by the chains' weight gradients
+            # ctx.x_recs[0]: the producer's record of x0, or the reduction wide_fwd(0) made
+            tag_amax(buf, torch.maximum(ctx.x_recs[0][0], R.amax(0)))
             return buf
 
         for k in range(L):
@@ -1199,12 +1212,8 @@ class DenseBlockFunction(torch.autograd.Function):
         try:
             return DenseBlockFunction._backward_impl(ctx, dbuf, G)
         finally:
-            # the raw kernels wrote into G without bumping its version counter: a record (or column sums) tagged onto the
-            # incoming tensor would still pass the version check
             if G is dbuf:
-                for tag in ("_otgan_amax", "_otgan_colsum"):
-                    if hasattr(dbuf, tag):
-                        delattr(dbuf, tag)
+                forget(dbuf)      # the raw kernels wrote into the incoming tensor (hand-offs: the rule above leave())
 
     @staticmethod
     def _backward_impl(ctx, dbuf, G):
@@ -1216,9 +1225,9 @@ class DenseBlockFunction(torch.autograd.Function):
         rows = N * H * W
         plan = ctx.plan
         if plan is not None and plan.get("h2") and ctx.batched and len(plan["wide"]) <= 2:
-            grads = DenseBlockFunction._backward_by_slice(ctx, buf, saved, G, dbuf, need_w)
+            grads = _backward_by_slice(ctx, buf, saved, G, dbuf, need_w)
             dx0 = _block_input_grad(G, C0) if ctx.needs_input_grad[0] else None
-            if dx0 is not None and _FUSED_AMAX and C0 % 4 == 0:
+            if dx0 is not None and C0 % 4 == 0:
                 tag_amax(dx0, ctx.dx0_rec)
             return (dx0, None, None, None, *grads)
         if plan is not None:
@@ -1227,24 +1236,10 @@ class DenseBlockFunction(torch.autograd.Function):
             dw_wide = [None] * len(plan["wide"])
 
             def wide_bwd(i, need_dx):
-                # channels [C0 + d0*F, Ctot) of G are final here: the group sees them through its wide convolution
-                wd, ops_ = plan["wide"][i], sw["wide"][i]
-                desc = wd["desc"]
-                src, gsrc = buf[..., wd["x_off"]:], G[..., wd["x_off"]:]
-                n_out = (L - wd["d0"]) * F
-                dy_rec = absmax_record_strided(G.data_ptr() + 4 * (C0 + wd["d0"] * F), rows, n_out, Ctot, G.device)
-                desc.x_amax, desc.x_amax_count = ctx.x_recs[i][0].data_ptr(), ctx.x_recs[i][1]
-                desc.dy_amax = dy_rec.data_ptr()
-                if need_w:
-                    dw = torch.empty_like(ops_["w"])
-                    conv_wgrad_raw(desc, src, None, G, dw)
-                    dw_wide[i] = dw          # [9][nrows][layers d0 ..][F], rows in the convolution's own order
-                if need_dx:
-                    if not ops_["bwd_done"]:
-                        ops_["bwd"], ops_["bwd_done"] = prepare_filters(desc, 1, ops_["w"]), True
-                    conv_dgrad_raw(desc, G, ops_["w"], src, None, gsrc, Ctot, True, ops_["bwd"])
-                desc.dy_amax = None
-                desc.x_amax_count = 0
+                # channels [C0 + d0*F, Ctot) of G are final here: one reduction of them for the two passes
+                d0 = plan["wide"][i]["d0"]
+                dy_rec = absmax_record_strided(G.data_ptr() + 4 * (C0 + d0 * F), rows, (L - d0) * F, Ctot, G.device)
+                dw_wide[i] = _wide_bwd(ctx, buf, G, i, need_w, need_dx, dy_rec)
 
             for k in reversed(range(L)):
                 for i in reversed(range(1, len(plan["wide"]))):
@@ -1261,21 +1256,7 @@ class DenseBlockFunction(torch.autograd.Function):
                     conv_dgrad_raw(desc, G, sw["w_g"][k], buf[..., off:], inv, G[..., off:], Ctot, True)
             wide_bwd(0, ctx.needs_input_grad[0])
             if need_w and ctx.batched and len(plan["wide"]) <= 2:
-                # the pieces of every layer's weight gradient where the passes left them (a column slice of each wide
-                # convolution's dw, in that convolution's row order, then the layer's own chain): one launch
-                parts = []
-                for k in range(L):
-                    pk = []
-                    for i, wd in enumerate(plan["wide"]):
-                        if wd["d0"] <= k:
-                            nl = L - wd["d0"]
-                            pk.append((dw_wide[i].data_ptr() + 4 * (k - wd["d0"]) * F, wd["back"], wd["nrows"], nl * F))
-                    if dw_g[k] is not None:
-                        pk.append((dw_g[k].data_ptr(), None, dw_g[k].shape[0] // 9, F))
-                    parts.append(pk)
-                dVs, dgs = weightnorm_bwd_block(saved[0::4], saved[1::4], saved[3::4], parts)
-                for k in range(L):
-                    grads[3 * k:3 * k + 2] = [dVs[k].view(ctx.vshapes[k]), dgs[k]]
+                _block_weight_grads(ctx, saved, grads, dw_g, dw_wide)
             elif need_w:
                 for k in range(L):
                     V2d, g, w, inv_norm = saved[4 * k:4 * k + 4]
@@ -1306,19 +1287,62 @@ class DenseBlockFunction(torch.autograd.Function):
                 # d/d(inputs of layer k) accumulates into the first Ck channels of G
                 conv_dgrad_raw(desc, G, w, buf, inv, G, Ctot, True)
             if need_w and ctx.batched:
-                parts = [[(dws[k].data_ptr(), None, dws[k].shape[0] // 9, F)] for k in range(L)]
-                dVs, dgs = weightnorm_bwd_block(saved[0::4], saved[1::4], saved[3::4], parts)
-                for k in range(L):
-                    grads[3 * k:3 * k + 2] = [dVs[k].view(ctx.vshapes[k]), dgs[k]]
+                _block_weight_grads(ctx, saved, grads, dws)
         if need_w:
-            # Layer k's output gradient G[..., Ck:Ck+F] is final once the layers after it have been
-            # processed, and no earlier layer writes there: all L bias gradients are the column sums
-            # of the finished G -- one reduction instead of L.
-            db_all = colsum(G.data_ptr() + 4 * C0, rows, L * F, Ctot, G.device)
-            for k in range(L):
-                grads[3 * k + 2] = db_all[k * F:(k + 1) * F]
+            _block_bias_grads(ctx, G, grads)
         dx0 = _block_input_grad(G, C0) if ctx.needs_input_grad[0] else None
         return (dx0, None, None, None, *grads)
+
+
+def _wide_bwd(ctx, buf, G, i, need_w, need_dx, dy_amax, dx_amax_out=None, wgrad_stream=None):
+    """Backward of wide convolution i of a split block, once the gradient of the channels it wrote ([C0 + d0*F, Ctot) of G)
+    is final: its weight gradient (returned: [9][nrows][layers d0 ..][F], rows in the convolution's own order; issued under
+    `wgrad_stream()` when given) and, with need_dx, its input gradient added into G.  dy_amax bounds those channels of G,
+    dx_amax_out receives the largest magnitude the input gradient writes; the record(s) of the input and the kept operand are
+    the forward launch's (ctx.x_recs, ctx.x_ops)."""
+    wd, ops_ = ctx.plan["wide"][i], ctx.sw["wide"][i]
+    src, gsrc = buf[..., wd["x_off"]:], G[..., wd["x_off"]:]
+    desc = launch_desc(wd["desc"], x_amax=ctx.x_recs[i], x_operand=ctx.x_ops[i], dy_amax=dy_amax)
+    dw = None
+    if need_w:
+        with (wgrad_stream() if wgrad_stream is not None else _NULL_CTX):
+            dw = torch.empty_like(ops_["w"])
+            conv_wgrad_raw(desc, src, None, G, dw)
+    if need_dx:
+        if not ops_["bwd_done"]:
+            ops_["bwd"], ops_["bwd_done"] = prepare_filters(desc, 1, ops_["w"]), True
+        conv_dgrad_raw(desc, G, ops_["w"], src, None, gsrc, G.shape[-1], True, ops_["bwd"], dx_amax_out=dx_amax_out)
+    return dw
+
+
+def _block_weight_grads(ctx, saved, grads, dw_g, dw_wide=()):
+    """grads[3 k], grads[3 k + 1] (dV, dg) of every layer of a dense block from the pieces of its weight gradient where the
+    passes left them -- a column slice of each wide convolution's dw, in that convolution's row order, then the layer's own
+    chain (dw_g[k]; the whole gradient when the block is not split) -- in one launch (weightnorm_bwd_block)."""
+    L, F = ctx.L, ctx.F
+    parts = []
+    for k in range(L):
+        pk = []
+        for wd, dw in zip(ctx.plan["wide"] if dw_wide else (), dw_wide):
+            if wd["d0"] <= k:
+                pk.append((dw.data_ptr() + 4 * (k - wd["d0"]) * F, wd["back"], wd["nrows"], (L - wd["d0"]) * F))
+        if dw_g[k] is not None:
+            pk.append((dw_g[k].data_ptr(), None, dw_g[k].shape[0] // 9, F))
+        parts.append(pk)
+    dVs, dgs = weightnorm_bwd_block(saved[0::4], saved[1::4], saved[3::4], parts)
+    for k in range(L):
+        grads[3 * k:3 * k + 2] = [dVs[k].view(ctx.vshapes[k]), dgs[k]]
+
+
+def _block_bias_grads(ctx, G, grads):
+    """grads[3 k + 2] of every layer of a dense block.  Layer k's output gradient G[..., Ck:Ck+F] is final once the layers
+    after it have been processed, and no earlier layer writes there: all L bias gradients are the column sums of the
+    finished G -- one reduction instead of L."""
+    L, C0, F = ctx.L, ctx.C0, ctx.F
+    Ctot = G.shape[-1]
+    db_all = colsum(G.data_ptr() + 4 * C0, G.numel() // Ctot, L * F, Ctot, G.device)
+    for k in range(L):
+        grads[3 * k + 2] = db_all[k * F:(k + 1) * F]
 
 
 def _block_input_grad(G, C0):
@@ -1374,7 +1398,6 @@ def _backward_by_slice(ctx, buf, saved, G, dbuf, need_w):
     L, C0, F = ctx.L, ctx.C0, ctx.F
     N, H, W, Ctot = buf.shape
     plan, sw = ctx.plan, ctx.sw
-    rows = N * H * W
     lib = _lib.lib()
     grads = [None] * (3 * L)
     dw_g = [None] * L
@@ -1397,7 +1420,7 @@ def _backward_by_slice(ctx, buf, saved, G, dbuf, need_w):
     # kernels that follow on this stream (they add into OTHER channels of G)
     side = SIDE_STREAM if need_w else None
     if side is not None:
-        for t in [G, buf, RR, R0] + [t for t in ctx.x_ops if t is not None] + ([ctx.fwd_recs[0]] if ctx.fwd_recs is not None else []):
+        for t in [G, buf, RR, R0, ctx.fwd_recs[0]] + [t for t in ctx.x_ops if t is not None]:
             t.record_stream(side)
 
     def wgrad_stream():
@@ -1407,26 +1430,11 @@ def _backward_by_slice(ctx, buf, saved, G, dbuf, need_w):
         return torch.cuda.stream(side)
 
     def wide_bwd(i, need_dx):
-        wd, ops_ = wides[i], sw["wide"][i]
-        desc = wd["desc"]
-        src, gsrc = buf[..., wd["x_off"]:], G[..., wd["x_off"]:]
-        desc.x_amax, desc.x_amax_count = ctx.x_recs[i][0].data_ptr(), ctx.x_recs[i][1]
-        desc.dy_amax, desc.dy_amax_count = RR[wd["d0"]].data_ptr(), L + 1 - wd["d0"]
-        if need_w:
-            with wgrad_stream():
-                dw = torch.empty_like(ops_["w"])
-                conv_wgrad_raw(desc, src, None, G, dw)
-            dw_wide[i] = dw
-        if need_dx:
-            if not ops_["bwd_done"]:
-                ops_["bwd"], ops_["bwd_done"] = prepare_filters(desc, 1, ops_["w"]), True
-            # i = 0 writes the block input's gradient (sums onto the incoming one): its own record, handed to the layer in
-            # front of the block with dx0 (round 4: that layer reduced the tensor itself)
-            desc.dx_amax_out = Rc.data_ptr() if i > 0 else R0.data_ptr()
-            conv_dgrad_raw(desc, G, ops_["w"], src, None, gsrc, Ctot, True, ops_["bwd"])
-            desc.dx_amax_out = None
-        desc.dy_amax = None
-        desc.dy_amax_count = desc.x_amax_count = 0
+        # the slices from d0 on and the incoming bound: rows [d0, L] of RR as they are.  i = 0 writes the block input's
+        # gradient (sums onto the incoming one): its own record, handed to the layer in front of the block with dx0
+        # (round 4: that layer reduced the tensor itself)
+        d0 = wides[i]["d0"]
+        dw_wide[i] = _wide_bwd(ctx, buf, G, i, need_w, need_dx, (RR[d0], L + 1 - d0), Rc if i > 0 else R0, wgrad_stream)
 
     starts = [wd["d0"] for wd in wides] + [L]
     for gi in reversed(range(len(wides))):
@@ -1446,43 +1454,20 @@ def _backward_by_slice(ctx, buf, saved, G, dbuf, need_w):
                 desc = ctx.descs[c]
                 cmap, _inv = ctx.maps[c]
                 off = C0 + plan["g0"][c] * F
+                # records of the slices the layer read (the rows its forward kernel read) and of its output gradient (the
+                # slices' rows from c on and the incoming bound): the kernel runs on the fp16 matrix pipe (round 4)
+                R, gbase, gidx = ctx.fwd_recs
                 with wgrad_stream():
                     dw_g[c] = torch.empty_like(sw["w_g"][c])
-                if ctx.fwd_recs is not None:
-                    # records of the slices the layer read (the rows its forward kernel read) and of its output gradient (the
-                    # slices' rows from c on and the incoming bound): the kernel runs on the fp16 matrix pipe (round 4)
-                    R, gbase, gidx = ctx.fwd_recs
-                    desc.x_amax = R[gbase[gidx[plan["g0"][c]]]].data_ptr()
-                    desc.x_amax_count = 1 + plan["own_len"][c]
-                    desc.dy_amax, desc.dy_amax_count = RR[c].data_ptr(), L + 1 - c
-                with wgrad_stream():
-                    conv_wgrad_raw(desc, buf[..., off:], cmap, G, dw_g[c])
-                desc.x_amax = desc.dy_amax = None
-                desc.x_amax_count = desc.dy_amax_count = 0
+                    conv_wgrad_raw(desc, buf[..., off:], cmap, G, dw_g[c], dy_amax=(RR[c], L + 1 - c),
+                                   x_amax=(R[gbase[gidx[plan["g0"][c]]]], 1 + plan["own_len"][c]))
     wide_bwd(0, ctx.needs_input_grad[0])
     if need_w:
         assert ctx.batched and len(wides) <= 2
-        parts = []
-        for k in range(L):
-            pk = []
-            for i, wd in enumerate(wides):
-                if wd["d0"] <= k:
-                    nl = L - wd["d0"]
-                    pk.append((dw_wide[i].data_ptr() + 4 * (k - wd["d0"]) * F, wd["back"], wd["nrows"], nl * F))
-            if dw_g[k] is not None:
-                pk.append((dw_g[k].data_ptr(), None, dw_g[k].shape[0] // 9, F))
-            parts.append(pk)
         with wgrad_stream():
-            dVs, dgs = weightnorm_bwd_block(saved[0::4], saved[1::4], saved[3::4], parts)
-            for k in range(L):
-                grads[3 * k:3 * k + 2] = [dVs[k].view(ctx.vshapes[k]), dgs[k]]
-            db_all = colsum(G.data_ptr() + 4 * C0, rows, L * F, Ctot, G.device)
-            for k in range(L):
-                grads[3 * k + 2] = db_all[k * F:(k + 1) * F]
+            _block_weight_grads(ctx, saved, grads, dw_g, dw_wide)
+            _block_bias_grads(ctx, G, grads)
     return grads
-
-
-DenseBlockFunction._backward_by_slice = staticmethod(_backward_by_slice)
 
 
 def dense_block_op(x0, segs0, params, ksize=3, preact=1):
@@ -1500,15 +1485,14 @@ class GluFunction(torch.autograd.Function):
         x = x.contiguous()
         C2 = x.shape[-1]
         rows = x.numel() // C2
-        pre = getattr(x, "_otgan_glu", None)
-        if pre is not None and pre[1] == x._version:
+        pre = take(x, "glu", remove=True)
+        if pre is not None:
             # the layer that produced x already wrote the gated product (Conv2dFunction, glu_hint)
-            del x._otgan_glu
             _PENDING_GLU[0] = None
             ctx.save_for_backward(x)
-            return pre[0]
+            return pre
         y = torch.empty(x.shape[:-1] + (C2 // 2,), dtype=x.dtype, device=x.device)
-        rec = amax_slot(x.device) if (_FUSED_AMAX and (C2 // 2) % 4 == 0) else None
+        rec = amax_slot(x.device) if (C2 // 2) % 4 == 0 else None
         _lib.check(_lib.lib().otgan_glu_fwd_amax_f32(x.data_ptr(), rows, C2 // 2, y.data_ptr(), _lib.ptr(rec),
                                                      _lib.stream_ptr()), "glu_fwd")
         if rec is not None:
@@ -1522,21 +1506,20 @@ class GluFunction(torch.autograd.Function):
         dy = dy.contiguous()
         C2 = x.shape[-1]
         dx = torch.empty_like(x)
-        rec = amax_slot(x.device) if (_FUSED_AMAX and (C2 // 2) % 4 == 0) else None
-        if _GLU_COLSUM and (C2 // 2) % 4 == 0:
+        if (C2 // 2) % 4 == 0:
+            rec = amax_slot(x.device)
             # dx is the output gradient of the convolution in front of the GLU: leave its column sums (that layer's
             # bias gradient) with it instead of reading dx once more there
             cs = torch.empty(C2, dtype=x.dtype, device=x.device)
             scratch = torch.empty(256 * C2, dtype=x.dtype, device=x.device)
             _lib.check(_lib.lib().otgan_glu_bwd_colsum_f32(x.data_ptr(), dy.data_ptr(), x.numel() // C2, C2 // 2,
-                                                           dx.data_ptr(), _lib.ptr(rec), cs.data_ptr(), scratch.data_ptr(),
+                                                           dx.data_ptr(), rec.data_ptr(), cs.data_ptr(), scratch.data_ptr(),
                                                            _lib.stream_ptr()), "glu_bwd_colsum")
-            dx._otgan_colsum = (cs, dx._version)
+            leave(dx, "colsum", cs)
+            tag_amax(dx, rec)
         else:
             _lib.check(_lib.lib().otgan_glu_bwd_amax_f32(x.data_ptr(), dy.data_ptr(), x.numel() // C2,
-                                                         C2 // 2, dx.data_ptr(), _lib.ptr(rec), _lib.stream_ptr()), "glu_bwd")
-        if rec is not None:
-            tag_amax(dx, rec)
+                                                         C2 // 2, dx.data_ptr(), None, _lib.stream_ptr()), "glu_bwd")
         return dx
 
 
@@ -1584,7 +1567,7 @@ class FeatureHeadFunction(torch.autograd.Function):
         df = df.contiguous()
         N, H, W, C = x.shape
         dx = torch.empty_like(x)
-        rec = amax_slot(x.device) if (_FUSED_AMAX and C % 4 == 0) else None
+        rec = amax_slot(x.device) if C % 4 == 0 else None
         _lib.check(_lib.lib().otgan_feature_head_bwd_amax_f32(x.data_ptr(), f.data_ptr(), norm.data_ptr(),
                                                               df.data_ptr(), N, H * W, C, dx.data_ptr(), _lib.ptr(rec),
                                                               _lib.stream_ptr()), "head_bwd")
@@ -1604,7 +1587,7 @@ class ConcatChannelsFunction(torch.autograd.Function):
     def forward(ctx, *xs):
         ctx.widths = [int(t.shape[-1]) for t in xs]
         y = torch.cat(xs, 3)
-        if _FUSED_AMAX and all(w % 4 == 0 for w in ctx.widths) and any(amax_of(t) is not None for t in xs):
+        if all(w % 4 == 0 for w in ctx.widths) and any(amax_of(t) is not None for t in xs):
             recs = [amax_of(t) if amax_of(t) is not None else absmax_record(t.contiguous()) for t in xs]
             rec = recs[0]
             for r in recs[1:]:
@@ -1639,9 +1622,9 @@ class ExtendChannelsFunction(torch.autograd.Function):
         base = grown_buffer(x, Ctot)
         assert base is not None
         ctx.widths = [int(t.shape[-1]) for t in (x,) + others]
-        # the records are read BEFORE the copies: x is a view of `base` and shares its version counter, so the in-place
-        # copies below make x's tag look stale (the record was never carried and the block reduced its input again)
-        rec = amax_of(x) if (_FUSED_AMAX and all(w % 4 == 0 for w in ctx.widths)) else None
+        # read before you write (hand-offs): x is a view of `base`, the in-place copies below make what it carries stale
+        # (the record was never carried and the block reduced its input again)
+        rec = amax_of(x) if all(w % 4 == 0 for w in ctx.widths) else None
         if rec is not None:
             for t in others:
                 r = amax_of(t)

@@ -76,8 +76,8 @@ def _critic_pair(dev, seed, strip):
 
     def maybe_strip(t):
         seen.append(ops.amax_of(t) is not None)
-        if strip and hasattr(t, "_otgan_amax"):
-            del t._otgan_amax
+        if strip:
+            ops.take(t, "amax", remove=True)
         return t
 
     y0 = maybe_strip(ops.conv2d_op(x, Vs[0], gs[0], bs[0], stride=1, preact=ops.ACT[None]))

@@ -28,6 +28,34 @@ def _rel(a, b):
     return float((a - b).norm() / b.norm().clamp_min(1e-30))
 
 
+# otgan_conv_desc fields that belong to ONE launch: a descriptor an autograd node keeps for its backward pass holds geometry
+# only (N ... list_quads, list_width); the launchers fill these in on a private copy (ops.launch_desc)
+PER_LAUNCH_FIELDS = ("x_amax", "x_amax_count", "dy_amax", "dy_amax_count", "w_amax", "y_amax_out", "dx_amax_out", "glu_out",
+                     "glu_amax_out", "y_accumulate", "x_operand")
+
+
+def _kept_descriptors(fn):
+    """The descriptors the node of a convolution (`.desc`) or of a dense block (`.descs`, the plan's wide ones) keeps, with
+    their bytes as they stand; asserts that every per-launch field is zero."""
+    if hasattr(fn, "desc"):
+        descs = [fn.desc]
+    else:
+        descs = [d for d in fn.descs if d is not None]
+        if fn.plan is not None:
+            descs += [wd["desc"] for wd in fn.plan["wide"]]
+    assert descs
+    for d in descs:
+        left = [f for f in PER_LAUNCH_FIELDS if getattr(d, f)]
+        assert not left, f"per-launch fields left set in a kept descriptor: {left}"
+    return descs, [bytes(d) for d in descs]
+
+
+def _filter_bytes(desc, which=0):
+    import ctypes
+    from otgan_amd import _lib
+    return _lib.lib().otgan_conv2d_filter_bytes(ctypes.byref(desc), which)
+
+
 CONV_CASES = [
     # name, N, H, W, segs, Cout, k, stride, upsample, preact
     ("s1_plain", 2, 8, 8, (16,), 32, 5, 1, False, None),
@@ -115,7 +143,8 @@ CONV_CASES = [
 
 @pytest.mark.parametrize("case", CONV_CASES, ids=[c[0] for c in CONV_CASES])
 def test_conv2d(dev, case):
-    from otgan_amd import ops
+    import ctypes
+    from otgan_amd import _lib, ops
     name, N, H, W, segs, Cout, k, stride, up, pre = case
     gen = torch.Generator().manual_seed(sum(map(ord, name)))
     C = sum(segs)
@@ -139,7 +168,20 @@ def test_conv2d(dev, case):
     y = ops.conv2d_op(x, V, g, b, stride=stride, upsample=up, preact=ops.ACT[pre], segs=segs)
     assert y.shape == y_ref.shape
     assert _rel(y, y_ref) < TOL, "forward"
+    fn = y.grad_fn
+    descs, kept = _kept_descriptors(fn)
+    if not any(os.environ.get(k) for k in ("OTGAN_WINO_FP32", "OTGAN_DISABLE_WINOGRAD")):
+        # the routes whose launches take the most per-launch fields: 5x5 stride 2 and wide 3x3 stride 1 on the Winograd
+        # passes (records of x and dy, kept operand), a list input on the implicit-GEMM passes (producer records only)
+        if name in ("wino_s2_plain", "s2_crelu", "wino_plain3_crelu"):
+            assert _filter_bytes(fn.desc) > 0 and fn.cmap is None and fn.x_rec is not None
+        if name == "list_crelu_s2":
+            assert _filter_bytes(fn.desc) == 0 and fn.cmap is not None and fn.x_rec is None
+        # the transformed input is kept for the weight gradient exactly where the library says the two passes share it
+        shares = _lib.lib().otgan_conv2d_operand_bytes(ctypes.byref(fn.desc)) > 0
+        assert (fn.x_op is not None) == (shares and fn.cmap is None and fn.filt["fwd"] is not None)
     dx, dV, dg, db = torch.autograd.grad(y, [x, V, g, b], dy64.float().to(dev))
+    assert [bytes(d) for d in descs] == kept, "the backward pass changed a kept descriptor"
     assert _rel(dx, dx_ref) < TOL, "dgrad"
     assert _rel(dV, grads_ref[len(segs)]) < TOL, "wgrad/dV"
     assert _rel(dg, grads_ref[len(segs) + 1]) < TOL, "dg"
@@ -470,8 +512,11 @@ def test_wino_outlier_zero_and_nan(dev):
 def test_dense_block_split_matches_chain(dev, case, monkeypatch):
     """A dense block computed as "block-input convolution (Winograd) + growth chain" (ops.DenseBlockFunction) against
     the fp64 oracle's plain chain of convolutions over the growing concatenation (reference nn.py:243-262), and
-    against the same op with the split switched off."""
-    from otgan_amd import ops
+    against the same op with the split switched off.  On both routes the descriptors the node keeps hold geometry only,
+    before and after the backward pass."""
+    import ctypes
+    from otgan_amd import _lib, ops
+    from otgan_amd._lib_layers import ConvDesc
     name, N, H, W, segs0, L, pre = case
     F = 16
     gen = torch.Generator().manual_seed(sum(map(ord, name)))
@@ -498,7 +543,17 @@ def test_dense_block_split_matches_chain(dev, case, monkeypatch):
         x0 = torch.cat([t.detach().float() for t in xs64], 3).to(dev).requires_grad_(True)
         params = [[t.detach().float().to(dev).requires_grad_(True) for t in p] for p in P64]
         y = ops.dense_block_op(x0, segs0, params, 3, ops.ACT[pre])
+        fn = y.grad_fn
+        # the split route is taken when the library gives the block-input convolution C0 -> L*F its Winograd passes
+        Ctot = C0 + L * F
+        d_in = ConvDesc(N, H, W, C0, Ctot, 0, 3, 3, 1, L * F, Ctot, C0, ops.ACT[pre], 1)
+        assert (fn.plan is not None) == (split and _filter_bytes(d_in) > 0)
+        if fn.plan is not None and fn.plan["h2"]:        # ... and its chains the fp16 kernels when it says so
+            probe = ops.launch_desc(next(d for d in fn.descs if d is not None), y_accumulate=1)
+            assert _lib.lib().otgan_dense16_h2_ok(ctypes.byref(probe)) == 1
+        descs, kept = _kept_descriptors(fn)
         grads = torch.autograd.grad(y, [x0] + [t for p in params for t in p], dy64.float().to(dev))
+        assert [bytes(d) for d in descs] == kept, "the backward pass changed a kept descriptor"
         return y, grads
 
     y_s, g_s = run(True)
@@ -766,12 +821,14 @@ def test_glu_in_output_transform(dev, shape):
     for hint in (False, True):
         x, V, g, b = (t.clone().requires_grad_(True) for t in (x0, V0, g0, b0))
         y = ops.conv2d_op(x, V, g, b, stride=1, upsample=True, preact=0, glu_hint=hint)
-        assert hasattr(y, "_otgan_glu") == hint
+        assert (ops.take(y, "glu") is not None) == hint
+        descs, kept = _kept_descriptors(y.grad_fn)       # (glu_out / glu_amax_out went to the launch, not into ctx.desc)
         z = ops.glu(y)
-        assert not hasattr(y, "_otgan_glu")
+        assert ops.take(y, "glu") is None
         rec = ops.amax_of(z)
         assert rec is not None
         z.backward(dz)
+        assert [bytes(d) for d in descs] == kept, "the backward pass changed a kept descriptor"
         res.append((y.detach(), z.detach(), rec.max().clone(), x.grad, V.grad, g.grad, b.grad))
     for a, c in zip(*res):
         assert torch.equal(a, c)
