@@ -2469,7 +2469,7 @@ WgPlan plan_wgrad(const otgan_conv_desc* d, const Geo& g) {
   const int taps = d->KH * d->KW;
   p.dense16 = false;
   if (d->Cout == 16 && d->KH == 3 && d->KW == 3 && d->stride == 1 && d->upsample == 0 && d->C % 4 == 0 &&
-      d->ldx % 4 == 0 && d->ldy % 4 == 0 && d->y_coff % 4 == 0 && dense16_enabled()) {
+      d->ldx % 4 == 0 && d->ldy % 4 == 0 && d->y_coff % 4 == 0) {
     const Dense16Tiling t = dense16_tiling(d->N, d->H, d->W, g.Ceff);
     if (t.ok) {
       memset(&p, 0, sizeof(p));
@@ -2857,7 +2857,7 @@ size_t otgan_conv2d_workspace_bytes(const otgan_conv_desc* d, int which) {
 static bool dense16_h2_desc_ok(const otgan_conv_desc* d) {
   return d && d->Cout == 16 && d->KH == 3 && d->KW == 3 && d->stride == 1 && d->upsample == 0 && d->preact == OTGAN_ACT_CRELU &&
          d->list_width == 16 && d->C >= 16 && d->C % 16 == 0 && d->ldx % 4 == 0 && d->y_accumulate && d->ldy % 4 == 0 &&
-         dense16_enabled() && dense16_h2_shape_ok(d->N, d->H, d->W);
+         dense16_h2_shape_ok(d->N, d->H, d->W);
 }
 int otgan_dense16_h2_ok(const otgan_conv_desc* d) { return dense16_h2_desc_ok(d) ? 1 : 0; }
 size_t otgan_dense16_filter_bytes(int nslices) { return dense16_h2_filter_bytes(nslices); }
@@ -2895,33 +2895,35 @@ int otgan_dense16_bwd_slice_f32(int N, int H, int W, int npairs, const float* g,
   OTGAN_CHECK_ARG(g && filters && x && dx && rec0 && nrec0 >= 1 && (rec1 || nrec1 == 0), "null pointer");
   OTGAN_CHECK_ARG(npairs >= 1 && ldg % 4 == 0 && ldx % 4 == 0 && aligned16(g) && aligned16(x) && aligned16(dx) && aligned16(filters),
                   "strides multiples of 4, 16-byte aligned buffers");
-  OTGAN_CHECK_ARG(dense16_enabled() && dense16_h2_shape_ok(N, H, W), "geometry not taken by the fp16 x 2 growth kernels");
+  OTGAN_CHECK_ARG(dense16_h2_shape_ok(N, H, W), "geometry not taken by the fp16 x 2 growth kernels");
   ProfScope ps(OTGAN_PROF_CONV_DGRAD, 2.0 * (double)N * H * W * 9.0 * 16.0 * npairs * 32.0, 0.0, (hipStream_t)stream);
   const int rc = dense16_bwd_h2(N, H, W, npairs, g, ldg, filters, x, ldx, dx, rec0, nrec0, rec1, nrec1, (hipStream_t)stream, amax_out);
   OTGAN_CHECK_LAUNCH("dense16 bwd slice");
   return rc;
 }
 
+// OTGAN_DENSE16_CHAIN=0, a test knob: the chains keep one launch per layer / slice (read once per process)
+static bool dense16_chain_one_launch() {
+  static const bool on = [] { const char* e = getenv("OTGAN_DENSE16_CHAIN"); return !(e && e[0] == '0'); }();
+  return on;
+}
 int otgan_dense16_chain_fwd_f32(int N, int H, int W, int nslices, float* buf_group, int ld, const void* const* filters,
                                 float* records, void* stream) {
   OTGAN_CHECK_ARG(buf_group && filters && records && nslices >= 2 && nslices <= 17 && ld % 4 == 0 && aligned16(buf_group),
                   "bad chain arguments");
-  OTGAN_CHECK_ARG(dense16_enabled() && dense16_h2_shape_ok(N, H, W), "geometry not taken by the fp16 x 2 growth kernels");
+  OTGAN_CHECK_ARG(dense16_h2_shape_ok(N, H, W), "geometry not taken by the fp16 x 2 growth kernels");
   hipStream_t s = (hipStream_t)stream;
   const int R = OTGAN_AMAX_RECORD_FLOATS;
   for (int j = 1; j < nslices; ++j)
     OTGAN_CHECK_ARG(filters[j - 1] && aligned16(filters[j - 1]), "null / misaligned filters of chain layer %d", j);
-  // one launch for the whole chain where a workgroup covers an image (round 6: dense16_chain_fwd_h2_kernel; OTGAN_DENSE16_CHAIN=0,
-  // a test knob, keeps the launch per layer)
-  static const bool one_launch = [] { const char* e = getenv("OTGAN_DENSE16_CHAIN"); return !(e && e[0] == '0'); }();
-  if (one_launch && H == W && (W == 8 || W == 16)) {
+  // one launch for the whole chain where a workgroup covers an image (round 6: dense16_chain_fwd_h2_kernel)
+  if (dense16_chain_one_launch() && dense16_chain_fwd_h2_takes(H, W, nslices)) {
     double flop = 0.0;
     for (int j = 1; j < nslices; ++j) flop += 2.0 * (double)N * H * W * 9.0 * 32.0 * j * 16.0;
     ProfScope ps(OTGAN_PROF_CONV_FWD, flop, 0.0, s);
-    if (dense16_chain_fwd_h2(N, H, W, nslices, buf_group, ld, filters, records, s)) {
-      OTGAN_CHECK_LAUNCH("dense16 chain fwd (one launch)");
-      return OTGAN_OK;
-    }
+    dense16_chain_fwd_h2(N, H, W, nslices, buf_group, ld, filters, records, s);
+    OTGAN_CHECK_LAUNCH("dense16 chain fwd (one launch)");
+    return OTGAN_OK;
   }
   for (int j = 1; j < nslices; ++j) {
     ProfScope ps(OTGAN_PROF_CONV_FWD, 2.0 * (double)N * H * W * 9.0 * 32.0 * j * 16.0, 0.0, s);
@@ -2937,19 +2939,17 @@ int otgan_dense16_chain_bwd_f32(int N, int H, int W, int nslices, float* g_group
   OTGAN_CHECK_ARG(g_group && x_group && filters && rec0 && slice_records && nslices >= 2 && nslices <= 17 && ldg % 4 == 0 &&
                       ldx % 4 == 0 && aligned16(g_group) && aligned16(x_group),
                   "bad chain arguments");
-  OTGAN_CHECK_ARG(dense16_enabled() && dense16_h2_shape_ok(N, H, W), "geometry not taken by the fp16 x 2 growth kernels");
+  OTGAN_CHECK_ARG(dense16_h2_shape_ok(N, H, W), "geometry not taken by the fp16 x 2 growth kernels");
   hipStream_t s = (hipStream_t)stream;
   const int R = OTGAN_AMAX_RECORD_FLOATS;
   for (int c = nslices - 2; c >= 0; --c) OTGAN_CHECK_ARG(filters[c] && aligned16(filters[c]), "null / misaligned filters of slice %d", c);
-  static const bool one_launch = [] { const char* e = getenv("OTGAN_DENSE16_CHAIN"); return !(e && e[0] == '0'); }();
-  if (one_launch && H == W && W == 8) {      // round 6: the slices last to first inside one workgroup per image (8 x 8: dense16.hip)
+  if (dense16_chain_one_launch() && dense16_chain_bwd_h2_takes(H, W, nslices)) {   // round 6: the slices last to first inside one workgroup per image
     double flop = 0.0;
     for (int c = nslices - 2; c >= 0; --c) flop += 2.0 * (double)N * H * W * 9.0 * 16.0 * (nslices - 1 - c) * 32.0;
     ProfScope ps(OTGAN_PROF_CONV_DGRAD, flop, 0.0, s);
-    if (dense16_chain_bwd_h2(N, H, W, nslices, g_group, ldg, x_group, ldx, filters, rec0, slice_records, s)) {
-      OTGAN_CHECK_LAUNCH("dense16 chain bwd (one launch)");
-      return OTGAN_OK;
-    }
+    dense16_chain_bwd_h2(N, H, W, nslices, g_group, ldg, x_group, ldx, filters, rec0, slice_records, s);
+    OTGAN_CHECK_LAUNCH("dense16 chain bwd (one launch)");
+    return OTGAN_OK;
   }
   for (int c = nslices - 2; c >= 0; --c) {
     const int nsl = nslices - 1 - c;
@@ -3114,7 +3114,7 @@ static int conv2d_fwd_body(const otgan_conv_desc* d, const float* x, const int32
   OTGAN_CHECK_ARG(x && wT && y, "null pointer");
   hipStream_t s = (hipStream_t)stream;
   const bool growth16 = d->Cout == 16 && d->KH == 3 && d->KW == 3 && d->stride == 1 && d->upsample == 0 && d->C % 8 == 0 &&
-                        d->ldx % 4 == 0 && aligned16(x) && aligned16(wT) && aligned16(cmap) && dense16_enabled();
+                        d->ldx % 4 == 0 && aligned16(x) && aligned16(wT) && aligned16(cmap);
   const bool wino_s2_fwd_taken = wino_s2_ok(d, g) && cmap == nullptr && aligned16(x) && aligned16(wT) && aligned16(y) &&
                                  aligned16(bias) && aligned16(workspace) && workspace &&
                                  workspace_bytes >= otgan_conv2d_workspace_bytes(d, 0);
@@ -3442,7 +3442,7 @@ static int conv2d_dgrad_body(const otgan_conv_desc* d, const float* dy, const fl
   }
   if (d->Cout == 16 && d->KH == 3 && d->KW == 3 && d->stride == 1 && d->upsample == 0 && d->ldy % 4 == 0 &&
       d->y_coff % 4 == 0 && d->C % 4 == 0 && d->ldx % 4 == 0 && lddx % 4 == 0 && aligned16(dy) && aligned16(w) &&
-      aligned16(x) && aligned16(dx) && dense16_enabled() && dense16_tiling(d->N, d->H, d->W, g.Ceff).ok) {
+      aligned16(x) && aligned16(dx) && dense16_tiling(d->N, d->H, d->W, g.Ceff).ok) {
     // DenseNet growth layer: dy tile in LDS, weights streamed, pos/neg halves combined in registers
     Dense16Geo dg;
     dg.N = d->N; dg.H = d->H; dg.W = d->W; dg.logH = ilog2_exact(d->H); dg.logW = ilog2_exact(d->W);

@@ -14,7 +14,6 @@ struct Dense16Geo {
   const int32_t* cmap;      // effective channel -> source channel | sign<<31 (nullable)
 };
 
-bool dense16_enabled();
 // y[pix, coff + n] (+)= bias[n] + sum_{tap, e} act(+-x[pix + tap, c(e)]) * wT[n][tap*Ceff + e]
 // amax_out (nullable): amax record (common.h) that max-accumulates the magnitudes of the values written
 int dense16_fwd(const Dense16Geo& g, const float* x, const float* wT, const float* bias, float* y,
@@ -28,10 +27,13 @@ size_t dense16_h2_filter_bytes(int nsl);
 bool dense16_h2_shape_ok(int N, int H, int W);
 int dense16_h2_prepare(const float* const* wT, const int* nsl, void* const* out, int count, hipStream_t s);
 // the chain of a group (layers 1 .. nslices - 1 over the slices in front of each) in ONE launch where a workgroup covers an
-// image (8 x 8, 16 x 16); false: shape not taken, the caller launches layer by layer
-bool dense16_chain_fwd_h2(int N, int H, int W, int nslices, float* buf, int ld, const void* const* filters, float* records,
+// image.  ..._takes: whether the shape runs that way (the one place that decides; the caller opens its profiler scope, which
+// counts a launch, only then); otherwise the caller launches layer by layer.  The launchers require ..._takes.
+bool dense16_chain_fwd_h2_takes(int H, int W, int nslices);
+bool dense16_chain_bwd_h2_takes(int H, int W, int nslices);
+void dense16_chain_fwd_h2(int N, int H, int W, int nslices, float* buf, int ld, const void* const* filters, float* records,
                           hipStream_t s);
-bool dense16_chain_bwd_h2(int N, int H, int W, int nslices, float* g, int ldg, const float* x, int ldx,
+void dense16_chain_bwd_h2(int N, int H, int W, int nslices, float* g, int ldg, const float* x, int ldx,
                           const void* const* filters, const float* rec0, float* slice_records, hipStream_t s);
 int dense16_fwd_h2(int N, int H, int W, int nsl, const float* x, int ldx, const void* wq, const float* rec, int nrec,
                    float* y, int ldy, int coff, hipStream_t s, float* amax_out);

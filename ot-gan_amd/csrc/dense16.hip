@@ -20,6 +20,8 @@
 
 #include <stdlib.h>
 
+#include <type_traits>
+
 namespace {
 
 typedef int i32x4 __attribute__((ext_vector_type(4)));
@@ -653,7 +655,7 @@ struct FwdH2Args {
   const float* rec;      // amax records of the input: nrec consecutive records (512 floats apart)
   int nrec;
   int nsl;               // source slices of 16 channels
-  int N, H, W, logW, ldx, ldy, coff, TR, RS;
+  int N, H, W, ldx, ldy, coff;
   float* amax;           // amax record of the sums written, or null
 };
 
@@ -708,170 +710,252 @@ __global__ __launch_bounds__(1024) void dense16_h2_prep_kernel(H2PrepArgs a) {
   }
 }
 
-template <int PT, int WW>
-__global__ __launch_bounds__(256, 2) void dense16_fwd_h2_kernel(FwdH2Args a) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char smemh[];
-  __shared__ float s_sc[2];
-  constexpr int WBYTES = kH2SliceU16 * 2;                    // prepared weights of one slice: 20 steps x 1 KiB
-  // the image width is a template parameter: tile rows, LDS row stride and plane size are then compile-time constants and the
-  // plane / piece / tile offsets of the fragment reads fold into the ds_read immediates (one address add per tap pair
-  // instead of one per read: 100 -> 10 per slice)
-  constexpr bool W8 = WW == 8;
-  constexpr int TR = 64 * PT / WW, RS = WW == 8 ? 16 : WW + 2, LOGW = WW == 8 ? 3 : WW == 16 ? 4 : WW == 32 ? 5 : 6;
-  constexpr int PLANE = (TR + 2) * RS * 32;                 // bytes of one (sign, piece) plane
-  constexpr int NIT = ((TR + 2) * WW * 4 + 255) / 256;      // staging passes: (TR + 2) x W pixels x 4 quads over 256 threads
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int p = lane & 15, g = lane >> 4;
-  const int tiles_per_img = a.H / TR;
-  const int n = blockIdx.x / tiles_per_img;
-  const int r0 = (blockIdx.x - n * tiles_per_img) * TR;
-  unsigned char* const smw = smemh + 4 * PLANE;             // the slice's weights behind the four planes
-  for (int i = tid; i < 4 * PLANE / 16; i += 256) reinterpret_cast<u32x4*>(smemh)[i] = u32x4{0u, 0u, 0u, 0u};
-  // input scale: the maximum of the records' sub-slots (bit patterns of non-negative floats: unsigned order)
-  if (wave == 0) {
-    unsigned mb = 0u;
-    for (int i = lane; i < 16 * a.nrec; i += 64) {
-      const unsigned v = reinterpret_cast<const unsigned*>(a.rec)[(long)(i >> 4) * (kAmaxSub * kAmaxSubStride) + (i & 15) * kAmaxSubStride];
-      mb = v > mb ? v : mb;
-    }
-    for (int o = 32; o; o >>= 1) {
-      const unsigned t = __shfl_xor(mb, o);
-      mb = t > mb ? t : mb;
-    }
-    if (lane == 0) {
-      const float amax = __uint_as_float(mb);
-      int e = 0;
-      if (amax > 0.f) e = __builtin_amdgcn_frexp_expf(amax);
-      const int ew = *reinterpret_cast<const int*>(a.wq);
-      s_sc[0] = (amax <= 3.0e38f) ? __builtin_ldexpf(1.f, 14 - e) : __builtin_nanf("");
-      s_sc[1] = (amax <= 3.0e38f) ? __builtin_ldexpf(1.f, e + ew - 28) : __builtin_nanf("");   // (a NaN record stays loud)
-    }
+// ---- device stages shared by the four fp16 x 2 kernels (per layer / one launch per chain, forward / input gradient) ----------
+// Tile constants.  The image width is a template parameter: tile rows, LDS row stride and plane size are then compile-time
+// constants and the plane / piece / tile offsets of the fragment reads fold into the ds_read immediates (one address add per
+// tap pair instead of one per read: 100 -> 10 per slice)
+template <int PT_, int WW_>
+struct H2Tile {
+  static constexpr int PT = PT_, WW = WW_;
+  static constexpr bool W8 = WW == 8;
+  static constexpr int TR = 64 * PT / WW, RS = W8 ? 16 : WW + 2, LOGW = WW == 8 ? 3 : WW == 16 ? 4 : WW == 32 ? 5 : 6;
+  static constexpr int PLANE = (TR + 2) * RS * 32;            // bytes of one (sign, piece) plane
+  static constexpr int NIT = ((TR + 2) * WW * 4 + 255) / 256;  // staging passes: (TR + 2) x W pixels x 4 quads over 256 threads
+  static constexpr int WBYTES = kH2SliceU16 * 2;              // prepared weights of one slice: 20 steps x 1 KiB
+};
+struct H2Lane {
+  int tid, lane, wave, p, g;
+  __device__ __forceinline__ H2Lane() : tid(threadIdx.x), lane(tid & 63), wave(tid >> 6), p(lane & 15), g(lane >> 4) {}
+};
+
+template <class T, int NPLANES>
+__device__ __forceinline__ void h2_zero_planes(unsigned char* smem, int tid) {
+  for (int i = tid; i < NPLANES * T::PLANE / 16; i += 256) reinterpret_cast<u32x4*>(smem)[i] = u32x4{0u, 0u, 0u, 0u};
+}
+// one wave: the maximum of the sub-slots of nrec0 + nrec1 records in two ranges (bit patterns of non-negative floats:
+// unsigned order), in every lane
+__device__ __forceinline__ unsigned h2_records_max(const float* rec0, int nrec0, const float* rec1, int nrec1, int lane) {
+  unsigned mb = 0u;
+  for (int i = lane; i < 16 * (nrec0 + nrec1); i += 64) {
+    const int r = i >> 4;
+    const float* base = r < nrec0 ? rec0 + (long)r * (kAmaxSub * kAmaxSubStride) : rec1 + (long)(r - nrec0) * (kAmaxSub * kAmaxSubStride);
+    const unsigned v = reinterpret_cast<const unsigned*>(base)[(i & 15) * kAmaxSubStride];
+    mb = v > mb ? v : mb;
   }
+  for (int o = 32; o; o >>= 1) {
+    const unsigned t = __shfl_xor(mb, o);
+    mb = t > mb ? t : mb;
+  }
+  return mb;
+}
+// one thread: bound of the operand (bits) and the weights' exponent (header of wq) -> s_sc[0] scale of the operand pieces,
+// s_sc[1] scale of the sums
+__device__ __forceinline__ void h2_set_scales(unsigned mb, const unsigned char* wq, float* s_sc) {
+  const float amax = __uint_as_float(mb);
+  int e = 0;
+  if (amax > 0.f) e = __builtin_amdgcn_frexp_expf(amax);
+  const int ew = *reinterpret_cast<const int*>(wq);
+  s_sc[0] = (amax <= 3.0e38f) ? __builtin_ldexpf(1.f, 14 - e) : __builtin_nanf("");
+  s_sc[1] = (amax <= 3.0e38f) ? __builtin_ldexpf(1.f, e + ew - 28) : __builtin_nanf("");   // (a NaN record stays loud)
+}
+// staging items of this thread: (pixel of the (TR + 2) x W band that starts one row above r0, quad of 4 channels); source
+// offset (floats, slice 0; negative: outside the image or the band) and LDS byte offset, computed once
+template <class T>
+__device__ __forceinline__ void h2_stage_offsets(int tid, long img_base, int r0, int H, int ld, long (&goff)[T::NIT], int (&loff)[T::NIT]) {
   const int slot = tid & 3;
-  const int total = (TR + 2) * WW * 4;
-  const long img_base = (long)n * a.H * WW;
-  const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
-  // staging items of this thread: (pixel of the (TR + 2) x W band, quad of 4 channels); source offset (floats, slice 0;
-  // negative: outside the image or the band) and LDS byte offset, computed once
-  long xoff[NIT];
-  int loff[NIT];
+  constexpr int total = (T::TR + 2) * T::WW * 4;
 #pragma unroll
-  for (int it = 0; it < NIT; ++it) {
+  for (int it = 0; it < T::NIT; ++it) {
     const int i = it * 256 + tid;
     const int px = i >> 2;
-    const int row = px >> LOGW, col = px & (WW - 1);
+    const int row = px >> T::LOGW, col = px & (T::WW - 1);
     const int ir = r0 - 1 + row;
-    const bool ok = i < total && (unsigned)ir < (unsigned)a.H;
-    xoff[it] = ok ? (img_base + (long)ir * WW + col) * a.ldx + 4 * slot : -1;
-    loff[it] = i < total ? (row * RS + col + 1) * 32 + slot * 8 : -1;
+    const bool ok = i < total && (unsigned)ir < (unsigned)H;
+    goff[it] = ok ? (img_base + (long)ir * T::WW + col) * ld + 4 * slot : -1;
+    loff[it] = i < total ? (row * T::RS + col + 1) * 32 + slot * 8 : -1;
   }
-  f32x4 R[NIT];
-  u32x4 WR[5];
-  const unsigned char* wsrc = a.wq + kH2HdrBytes + tid * 16;
-  auto stage_load = [&](int sl) {
+}
+// Weights of a slice: twenty 1 KiB steps (sign, tap pair, piece), each the 64 lanes' 16-byte MFMA operands in lane order.
+// They travel with the activations: loaded (coalesced, L2 hits) while the previous slice is multiplied, stored into LDS
+// behind the planes, read back as two ds_read_b128 per step -- the matrix loop waits on LDS only, never on memory
+// (a first version read them from global memory inside the loop: ten exposed L2 latencies per slice, 73 us; a register
+// ring three steps ahead: 59 us, but its loads queue behind the next slice's activation loads in vmcnt order).
+template <class T>
+__device__ __forceinline__ void h2_load_slice(const float* src, const long (&goff)[T::NIT], const unsigned char* wsrc, int sl,
+                                              f32x4 (&R)[T::NIT], u32x4 (&WR)[5]) {
+  const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-    for (int it = 0; it < NIT; ++it) R[it] = xoff[it] >= 0 ? *reinterpret_cast<const f32x4*>(a.x + xoff[it] + 16 * sl) : zero;
+  for (int it = 0; it < T::NIT; ++it) R[it] = goff[it] >= 0 ? *reinterpret_cast<const f32x4*>(src + goff[it] + 16 * sl) : zero;
 #pragma unroll
-    for (int q = 0; q < 5; ++q) WR[q] = *reinterpret_cast<const u32x4*>(wsrc + (long)sl * WBYTES + q * 4096);
-  };
-  auto stage_store = [&](float sx) {
+  for (int q = 0; q < 5; ++q) WR[q] = *reinterpret_cast<const u32x4*>(wsrc + (long)sl * T::WBYTES + q * 4096);
+}
+__device__ __forceinline__ void h2_store_weights(unsigned char* smw, int tid, const u32x4 (&WR)[5]) {
 #pragma unroll
-    for (int it = 0; it < NIT; ++it) {
-      if (loff[it] >= 0) {
-        unsigned wd[4][2];       // [plane: +hi, +lo, -hi, -lo][element pair]
+  for (int q = 0; q < 5; ++q) *reinterpret_cast<u32x4*>(smw + q * 4096 + tid * 16) = WR[q];
+}
+// forward: four planes [+hi, +lo, -hi, -lo] of the staged slice times sx
+template <class T>
+__device__ __forceinline__ void h2_store_signed(unsigned char* smem, const int (&loff)[T::NIT], const f32x4 (&R)[T::NIT], float sx) {
 #pragma unroll
-        for (int h = 0; h < 2; ++h) {
-          const d16_f2 v = d16_f2{R[it][2 * h], R[it][2 * h + 1]} * sx;
-          const d16_h2 hi = __builtin_convertvector(v, d16_h2);
-          const d16_h2 lo = __builtin_convertvector(v - __builtin_convertvector(hi, d16_f2), d16_h2);
-          const d16_h2 z = {(_Float16)0.f, (_Float16)0.f};
-          // relu(x) = hi+ + lo+, relu(-x) = hi- + lo- from the same two pieces (fp16 negation is exact): the sign of hi
-          // decides per element (hi = 0: |x 2^sx| < 2^-25, both sides take the sub-ulp lo piece or drop it -- 2^-39 of amax)
-          typedef short d16_s2 __attribute__((ext_vector_type(2)));
-          const unsigned neg = __builtin_bit_cast(unsigned, (d16_s2)(__builtin_bit_cast(d16_s2, hi) >> 15));   // 0xffff per negative half
-          const unsigned lb = __builtin_bit_cast(unsigned, lo);
-          wd[0][h] = __builtin_bit_cast(unsigned, __builtin_elementwise_max(hi, z));
-          wd[1][h] = lb & ~neg;
-          wd[2][h] = __builtin_bit_cast(unsigned, __builtin_elementwise_max(-hi, z));
-          wd[3][h] = (lb ^ 0x80008000u) & neg;
-        }
-        unsigned char* dst = smemh + loff[it];
+  for (int it = 0; it < T::NIT; ++it) {
+    if (loff[it] >= 0) {
+      unsigned wd[4][2];       // [plane: +hi, +lo, -hi, -lo][element pair]
 #pragma unroll
-        for (int q = 0; q < 4; ++q) *reinterpret_cast<u32x2*>(dst + q * PLANE) = u32x2{wd[q][0], wd[q][1]};
+      for (int h = 0; h < 2; ++h) {
+        const d16_f2 v = d16_f2{R[it][2 * h], R[it][2 * h + 1]} * sx;
+        const d16_h2 hi = __builtin_convertvector(v, d16_h2);
+        const d16_h2 lo = __builtin_convertvector(v - __builtin_convertvector(hi, d16_f2), d16_h2);
+        const d16_h2 z = {(_Float16)0.f, (_Float16)0.f};
+        // relu(x) = hi+ + lo+, relu(-x) = hi- + lo- from the same two pieces (fp16 negation is exact): the sign of hi
+        // decides per element (hi = 0: |x 2^sx| < 2^-25, both sides take the sub-ulp lo piece or drop it -- 2^-39 of amax)
+        typedef short d16_s2 __attribute__((ext_vector_type(2)));
+        const unsigned neg = __builtin_bit_cast(unsigned, (d16_s2)(__builtin_bit_cast(d16_s2, hi) >> 15));   // 0xffff per negative half
+        const unsigned lb = __builtin_bit_cast(unsigned, lo);
+        wd[0][h] = __builtin_bit_cast(unsigned, __builtin_elementwise_max(hi, z));
+        wd[1][h] = lb & ~neg;
+        wd[2][h] = __builtin_bit_cast(unsigned, __builtin_elementwise_max(-hi, z));
+        wd[3][h] = (lb ^ 0x80008000u) & neg;
       }
-    }
+      unsigned char* dst = smem + loff[it];
 #pragma unroll
-    for (int q = 0; q < 5; ++q) *reinterpret_cast<u32x4*>(smw + q * 4096 + tid * 16) = WR[q];
-  };
-  int ab[PT];
-#pragma unroll
-  for (int t = 0; t < PT; ++t) {
-    const int q0 = (wave * PT + t) * 16;
-    int rr, cc;
-    if (W8) {
-      rr = (q0 >> 3) + (p >> 3);
-      cc = p & 7;
-    } else {
-      rr = q0 >> LOGW;
-      cc = (q0 & (WW - 1)) + p;
+      for (int q = 0; q < 4; ++q) *reinterpret_cast<u32x2*>(dst + q * T::PLANE) = u32x2{wd[q][0], wd[q][1]};
     }
-    ab[t] = ((rr + 1) * RS + cc + 1) * 32 + 16 * (g & 1);
   }
+}
+// input gradient: two planes [hi, lo] of the staged slice times sd (no activation, one sign)
+template <class T>
+__device__ __forceinline__ void h2_store_plain(unsigned char* smem, const int (&loff)[T::NIT], const f32x4 (&R)[T::NIT], float sd) {
+#pragma unroll
+  for (int it = 0; it < T::NIT; ++it) {
+    if (loff[it] >= 0) {
+      unsigned wd[2][2];
+#pragma unroll
+      for (int h = 0; h < 2; ++h) {
+        const d16_f2 v = d16_f2{R[it][2 * h], R[it][2 * h + 1]} * sd;
+        const d16_h2 hi = __builtin_convertvector(v, d16_h2);
+        const d16_h2 lo = __builtin_convertvector(v - __builtin_convertvector(hi, d16_f2), d16_h2);
+        wd[0][h] = __builtin_bit_cast(unsigned, hi);
+        wd[1][h] = __builtin_bit_cast(unsigned, lo);
+      }
+      unsigned char* dst = smem + loff[it];
+      *reinterpret_cast<u32x2*>(dst) = u32x2{wd[0][0], wd[0][1]};
+      *reinterpret_cast<u32x2*>(dst + T::PLANE) = u32x2{wd[1][0], wd[1][1]};
+    }
+  }
+}
+// LDS byte offset of this lane's fragment row in each of the wave's PT pixel tiles (centre tap, k-group parity)
+template <class T>
+__device__ __forceinline__ void h2_frag_bases(const H2Lane& ln, int (&ab)[T::PT]) {
+#pragma unroll
+  for (int t = 0; t < T::PT; ++t) {
+    const int q0 = (ln.wave * T::PT + t) * 16;
+    int rr, cc;
+    if (T::W8) {
+      rr = (q0 >> 3) + (ln.p >> 3);
+      cc = ln.p & 7;
+    } else {
+      rr = q0 >> T::LOGW;
+      cc = (q0 & (T::WW - 1)) + ln.p;
+    }
+    ab[t] = ((rr + 1) * T::RS + cc + 1) * 32 + 16 * (ln.g & 1);
+  }
+}
+// LDS byte shift of this lane's tap of pair tp (the ninth tap has no partner: its upper k-groups re-read tap 8 against zero weights)
+template <class T>
+__device__ __forceinline__ int h2_tap_shift(const H2Lane& ln, int tp) {
+  const int t0 = 2 * tp, t1 = (2 * tp + 1 < 9) ? 2 * tp + 1 : 8;
+  const int sh0 = ((t0 / 3 - 1) * T::RS + (t0 % 3 - 1)) * 32;
+  const int sh1 = ((t1 / 3 - 1) * T::RS + (t1 % 3 - 1)) * 32;
+  return (ln.g >> 1) ? sh1 : sh0;
+}
+// pixel (row of the [N H W, ld] buffers) of accumulator element r of the wave's tile t; m0: first pixel of the workgroup
+template <class T>
+__device__ __forceinline__ long h2_out_pixel(const H2Lane& ln, long m0, int t, int r) {
+  return m0 + (ln.wave * T::PT + t) * 16 + 4 * ln.g + r;
+}
+// one-launch chains: the workgroup's own maximum bounds what its next trips read of the slice just written; the global record
+// for the later consumers.
+// (the slice just written is read back by other waves of THIS workgroup in the next trip: the barrier at the top of the loop
+// orders the stores before those loads -- workgroup scope, the vector cache is shared by the workgroup's waves; an
+// agent-scope release here would write the whole L2 back once per layer and workgroup)
+__device__ __forceinline__ void h2_chain_commit(unsigned* s_run, float* rec, unsigned omax, int lane) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const unsigned w = (unsigned)__shfl_xor((int)omax, o, 64);
+    omax = w > omax ? w : omax;
+  }
+  if (lane == 0) atomicMax(&s_run[0], omax);
+  amax_commit(rec, omax);
+}
+
+// forward, one source slice out of LDS: 10 steps (sign, tap pair) x 3 MFMAs per pixel tile
+template <class T>
+__device__ __forceinline__ void h2_fwd_step(const H2Lane& ln, const unsigned char* smem, const unsigned char* smw, const int (&ab)[T::PT],
+                                            f32x4 (&acc)[T::PT]) {
+  constexpr int PT = T::PT;
+#pragma unroll
+  for (int st = 0; st < 10; ++st) {
+    const int sign = st / 5, tp = st % 5;
+    const unsigned char* plane = smem + 2 * sign * T::PLANE;
+    const d16_h8 Bh = *reinterpret_cast<const d16_h8*>(smw + st * 2048 + ln.lane * 16);
+    const d16_h8 Bl = *reinterpret_cast<const d16_h8*>(smw + st * 2048 + 1024 + ln.lane * 16);
+    const int sh = h2_tap_shift<T>(ln, tp);
+    d16_h8 Ah[PT], Al[PT];
+#pragma unroll
+    for (int t = 0; t < PT; ++t) {
+      const unsigned char* ap = plane + ab[t] + sh;
+      Ah[t] = *reinterpret_cast<const d16_h8*>(ap);
+      Al[t] = *reinterpret_cast<const d16_h8*>(ap + T::PLANE);
+    }
+    // term-major: consecutive matrix instructions never share an accumulator (smallest terms first)
+#pragma unroll
+    for (int t = 0; t < PT; ++t) acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(Al[t], Bh, acc[t], 0, 0, 0);
+#pragma unroll
+    for (int t = 0; t < PT; ++t) acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(Ah[t], Bl, acc[t], 0, 0, 0);
+#pragma unroll
+    for (int t = 0; t < PT; ++t) acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(Ah[t], Bh, acc[t], 0, 0, 0);
+  }
+}
+// One growth layer on this workgroup's band: y[band pixels][coff ..+16] += conv3x3(crelu(slices 0 .. nsl - 1 of x)).  x: first
+// channel of the first slice; s_sc: set by one thread before the first barrier in here (which also completes the zero fill).
+// Returns the bits of the largest magnitude this thread wrote.
+// The K loop over source slices, two barriers per slice: load slice sl + 1 into registers, multiply slice sl out of LDS,
+// barrier, split and store what was loaded, barrier.  (The loop is written out here and in h2_bwd_layer rather than shared
+// through callables: handed over as lambdas, the forward kernels' register allocation moved across an occupancy step.)
+template <class T>
+__device__ __forceinline__ unsigned h2_fwd_layer(const H2Lane& ln, unsigned char* smem, const float* s_sc, const float* x,
+                                                 const long (&xoff)[T::NIT], const int (&loff)[T::NIT], const int (&ab)[T::PT],
+                                                 const unsigned char* wq, int nsl, float* y, int ldy, int coff, long m0) {
+  constexpr int PT = T::PT;
+  unsigned char* const smw = smem + 4 * T::PLANE;             // the slice's weights behind the four planes
+  const unsigned char* wsrc = wq + kH2HdrBytes + ln.tid * 16;
+  f32x4 R[T::NIT];
+  u32x4 WR[5];
   f32x4 acc[PT];
 #pragma unroll
-  for (int t = 0; t < PT; ++t) acc[t] = zero;
-  const int hiTap = g >> 1;
-  // Weights of a slice: twenty 1 KiB steps (sign, tap pair, piece), each the 64 lanes' 16-byte MFMA operands in lane order.
-  // They travel with the activations: loaded (coalesced, L2 hits) while the previous slice is multiplied, stored into LDS
-  // behind the planes, read back as two ds_read_b128 per step -- the matrix loop waits on LDS only, never on memory
-  // (a first version read them from global memory inside the loop: ten exposed L2 latencies per slice, 73 us; a register
-  // ring three steps ahead: 59 us, but its loads queue behind the next slice's activation loads in vmcnt order).
-  stage_load(0);
-  __syncthreads();               // zero fill and scales complete
-  const float sx = s_sc[0];
-  stage_store(sx);
-  __syncthreads();
-  const long m0 = (img_base + (long)r0 * WW);
+  for (int t = 0; t < PT; ++t) acc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
   float yv[PT][4];
-  for (int sl = 0; sl < a.nsl; ++sl) {
-    const bool more = sl + 1 < a.nsl;
+  h2_load_slice<T>(x, xoff, wsrc, 0, R, WR);
+  __syncthreads();
+  const float sx = s_sc[0];
+  h2_store_signed<T>(smem, loff, R, sx);
+  h2_store_weights(smw, ln.tid, WR);
+  __syncthreads();
+  for (int sl = 0; sl < nsl; ++sl) {
+    const bool more = sl + 1 < nsl;
     if (more) {
-      stage_load(sl + 1);
-    } else {
-      // the sums this workgroup adds onto: fetched under the last slice's matrix work
+      h2_load_slice<T>(x, xoff, wsrc, sl + 1, R, WR);
+    } else {   // the sums this workgroup adds onto: fetched under the last slice's matrix work
 #pragma unroll
       for (int t = 0; t < PT; ++t)
 #pragma unroll
-        for (int r = 0; r < 4; ++r) yv[t][r] = a.y[(m0 + (wave * PT + t) * 16 + 4 * g + r) * a.ldy + a.coff + p];
+        for (int r = 0; r < 4; ++r) yv[t][r] = y[h2_out_pixel<T>(ln, m0, t, r) * ldy + coff + ln.p];
     }
-#pragma unroll
-    for (int st = 0; st < 10; ++st) {
-      const int sign = st / 5, tp = st % 5;
-      const unsigned char* plane = smemh + 2 * sign * PLANE;
-      const d16_h8 Bh = *reinterpret_cast<const d16_h8*>(smw + st * 2048 + lane * 16);
-      const d16_h8 Bl = *reinterpret_cast<const d16_h8*>(smw + st * 2048 + 1024 + lane * 16);
-      const int t0 = 2 * tp, t1 = (2 * tp + 1 < 9) ? 2 * tp + 1 : 8;    // (the ninth tap's partner: tap 8 against zero weights)
-      const int sh0 = ((t0 / 3 - 1) * RS + (t0 % 3 - 1)) * 32;
-      const int sh1 = ((t1 / 3 - 1) * RS + (t1 % 3 - 1)) * 32;
-      const int sh = hiTap ? sh1 : sh0;
-      d16_h8 Ah[PT], Al[PT];
-#pragma unroll
-      for (int t = 0; t < PT; ++t) {
-        const unsigned char* ap = plane + ab[t] + sh;
-        Ah[t] = *reinterpret_cast<const d16_h8*>(ap);
-        Al[t] = *reinterpret_cast<const d16_h8*>(ap + PLANE);
-      }
-      // term-major: consecutive matrix instructions never share an accumulator (smallest terms first)
-#pragma unroll
-      for (int t = 0; t < PT; ++t) acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(Al[t], Bh, acc[t], 0, 0, 0);
-#pragma unroll
-      for (int t = 0; t < PT; ++t) acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(Ah[t], Bl, acc[t], 0, 0, 0);
-#pragma unroll
-      for (int t = 0; t < PT; ++t) acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(Ah[t], Bh, acc[t], 0, 0, 0);
-    }
+    h2_fwd_step<T>(ln, smem, smw, ab, acc);
     __syncthreads();
     if (more) {
-      stage_store(sx);
+      h2_store_signed<T>(smem, loff, R, sx);
+      h2_store_weights(smw, ln.tid, WR);
       __syncthreads();
     }
   }
@@ -881,12 +965,34 @@ __global__ __launch_bounds__(256, 2) void dense16_fwd_h2_kernel(FwdH2Args a) {
   for (int t = 0; t < PT; ++t)
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
-      const long m = m0 + (wave * PT + t) * 16 + 4 * g + r;
       const float o = fmaf(acc[t][r], so, yv[t][r]);          // the chains add onto the wide convolutions' sums
-      a.y[m * a.ldy + a.coff + p] = o;
+      y[h2_out_pixel<T>(ln, m0, t, r) * ldy + coff + ln.p] = o;
       const unsigned ob = amax_bits(o);
       omax = ob > omax ? ob : omax;
     }
+  return omax;
+}
+
+template <int PT, int WW>
+__global__ __launch_bounds__(256, 2) void dense16_fwd_h2_kernel(FwdH2Args a) {
+  using T = H2Tile<PT, WW>;
+  extern __shared__ __attribute__((aligned(16))) unsigned char smemh[];
+  __shared__ float s_sc[2];
+  const H2Lane ln;
+  const int tiles_per_img = a.H / T::TR;
+  const int n = blockIdx.x / tiles_per_img;
+  const int r0 = (blockIdx.x - n * tiles_per_img) * T::TR;
+  h2_zero_planes<T, 4>(smemh, ln.tid);
+  if (ln.wave == 0) {   // input scale: from the records of the slices read
+    const unsigned mb = h2_records_max(a.rec, a.nrec, a.rec, 0, ln.lane);
+    if (ln.lane == 0) h2_set_scales(mb, a.wq, s_sc);
+  }
+  const long img_base = (long)n * a.H * WW;
+  long xoff[T::NIT];
+  int loff[T::NIT], ab[PT];
+  h2_stage_offsets<T>(ln.tid, img_base, r0, a.H, a.ldx, xoff, loff);
+  h2_frag_bases<T>(ln, ab);
+  const unsigned omax = h2_fwd_layer<T>(ln, smemh, s_sc, a.x, xoff, loff, ab, a.wq, a.nsl, a.y, a.ldy, a.coff, img_base + (long)r0 * WW);
   if (a.amax) amax_commit(a.amax, omax);
 }
 
@@ -911,185 +1017,28 @@ struct ChainH2Args {
 };
 template <int PT, int WW>
 __global__ __launch_bounds__(256, 2) void dense16_chain_fwd_h2_kernel(ChainH2Args a) {
+  using T = H2Tile<PT, WW>;
   extern __shared__ __attribute__((aligned(16))) unsigned char smemh[];
   __shared__ float s_sc[2];
   __shared__ unsigned s_run[2];                              // [0] bits of the largest magnitude this workgroup wrote; [1] base records
-  constexpr int NIT = PT + 1;
-  constexpr int WBYTES = kH2SliceU16 * 2;
-  constexpr bool W8 = WW == 8;
-  constexpr int TR = 64 * PT / WW, RS = WW == 8 ? 16 : WW + 2, LOGW = WW == 8 ? 3 : WW == 16 ? 4 : 5;
-  constexpr int PLANE = (TR + 2) * RS * 32;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int p = lane & 15, g = lane >> 4;
+  const H2Lane ln;
   const int n = blockIdx.x;                                  // one workgroup per image (TR == H)
-  unsigned char* const smw = smemh + 4 * PLANE;
-  for (int i = tid; i < 4 * PLANE / 16; i += 256) reinterpret_cast<u32x4*>(smemh)[i] = u32x4{0u, 0u, 0u, 0u};
-  if (wave == 0) {                                           // records final before the launch: the wide sums and slice 0
-    unsigned mb = 0u;
-    for (int i = lane; i < 16 * 2; i += 64) {
-      const unsigned v = reinterpret_cast<const unsigned*>(a.rec)[(long)(i >> 4) * (kAmaxSub * kAmaxSubStride) + (i & 15) * kAmaxSubStride];
-      mb = v > mb ? v : mb;
-    }
-    for (int o = 32; o; o >>= 1) {
-      const unsigned t = __shfl_xor(mb, o);
-      mb = t > mb ? t : mb;
-    }
-    if (lane == 0) { s_run[0] = 0u; s_run[1] = mb; }
+  h2_zero_planes<T, 4>(smemh, ln.tid);
+  if (ln.wave == 0) {                                        // records final before the launch: the wide sums and slice 0
+    const unsigned mb = h2_records_max(a.rec, 2, a.rec, 0, ln.lane);
+    if (ln.lane == 0) { s_run[0] = 0u; s_run[1] = mb; }
   }
-  const int slot = tid & 3;
-  const int total = (TR + 2) * WW * 4;
   const long img_base = (long)n * a.H * WW;
-  const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
-  long xoff[NIT];
-  int loff[NIT];
-#pragma unroll
-  for (int it = 0; it < NIT; ++it) {
-    const int i = it * 256 + tid;
-    const int px = i >> 2;
-    const int row = px >> LOGW, col = px & (WW - 1);
-    const int ir = row - 1;                                  // (r0 = 0: the band is the image with one halo row above and below)
-    const bool ok = i < total && (unsigned)ir < (unsigned)a.H;
-    xoff[it] = ok ? (img_base + (long)ir * WW + col) * a.ld + 4 * slot : -1;
-    loff[it] = i < total ? (row * RS + col + 1) * 32 + slot * 8 : -1;
-  }
-  int ab[PT];
-#pragma unroll
-  for (int t = 0; t < PT; ++t) {
-    const int q0 = (wave * PT + t) * 16;
-    int rr, cc;
-    if (W8) {
-      rr = (q0 >> 3) + (p >> 3);
-      cc = p & 7;
-    } else {
-      rr = q0 >> LOGW;
-      cc = (q0 & (WW - 1)) + p;
-    }
-    ab[t] = ((rr + 1) * RS + cc + 1) * 32 + 16 * (g & 1);
-  }
-  const int hiTap = g >> 1;
-  const long m0 = img_base;
-  const float* const x = a.buf;
+  long xoff[T::NIT];
+  int loff[T::NIT], ab[PT];
+  h2_stage_offsets<T>(ln.tid, img_base, 0, a.H, a.ld, xoff, loff);   // (the band is the image with one halo row above and below)
+  h2_frag_bases<T>(ln, ab);
   for (int j = 1; j < a.nslices; ++j) {
     const unsigned char* const wq = a.wq[j - 1];
     __syncthreads();               // the zero fill (first trip) / the previous layer's LDS reads and s_run update are complete
-    if (tid == 0) {
-      const unsigned mb = s_run[0] > s_run[1] ? s_run[0] : s_run[1];
-      const float amax = __uint_as_float(mb);
-      int e = 0;
-      if (amax > 0.f) e = __builtin_amdgcn_frexp_expf(amax);
-      const int ew = *reinterpret_cast<const int*>(wq);
-      s_sc[0] = (amax <= 3.0e38f) ? __builtin_ldexpf(1.f, 14 - e) : __builtin_nanf("");
-      s_sc[1] = (amax <= 3.0e38f) ? __builtin_ldexpf(1.f, e + ew - 28) : __builtin_nanf("");
-    }
-    f32x4 R[NIT];
-    u32x4 WR[5];
-    const unsigned char* wsrc = wq + kH2HdrBytes + tid * 16;
-    auto stage_load = [&](int sl) {
-#pragma unroll
-      for (int it = 0; it < NIT; ++it) R[it] = xoff[it] >= 0 ? *reinterpret_cast<const f32x4*>(x + xoff[it] + 16 * sl) : zero;
-#pragma unroll
-      for (int q = 0; q < 5; ++q) WR[q] = *reinterpret_cast<const u32x4*>(wsrc + (long)sl * WBYTES + q * 4096);
-    };
-    auto stage_store = [&](float sx) {
-#pragma unroll
-      for (int it = 0; it < NIT; ++it) {
-        if (loff[it] >= 0) {
-          unsigned wd[4][2];
-#pragma unroll
-          for (int h = 0; h < 2; ++h) {
-            const d16_f2 v = d16_f2{R[it][2 * h], R[it][2 * h + 1]} * sx;
-            const d16_h2 hi = __builtin_convertvector(v, d16_h2);
-            const d16_h2 lo = __builtin_convertvector(v - __builtin_convertvector(hi, d16_f2), d16_h2);
-            const d16_h2 z = {(_Float16)0.f, (_Float16)0.f};
-            typedef short d16_s2 __attribute__((ext_vector_type(2)));
-            const unsigned neg = __builtin_bit_cast(unsigned, (d16_s2)(__builtin_bit_cast(d16_s2, hi) >> 15));
-            const unsigned lb = __builtin_bit_cast(unsigned, lo);
-            wd[0][h] = __builtin_bit_cast(unsigned, __builtin_elementwise_max(hi, z));
-            wd[1][h] = lb & ~neg;
-            wd[2][h] = __builtin_bit_cast(unsigned, __builtin_elementwise_max(-hi, z));
-            wd[3][h] = (lb ^ 0x80008000u) & neg;
-          }
-          unsigned char* dst = smemh + loff[it];
-#pragma unroll
-          for (int q = 0; q < 4; ++q) *reinterpret_cast<u32x2*>(dst + q * PLANE) = u32x2{wd[q][0], wd[q][1]};
-        }
-      }
-#pragma unroll
-      for (int q = 0; q < 5; ++q) *reinterpret_cast<u32x4*>(smw + q * 4096 + tid * 16) = WR[q];
-    };
-    f32x4 acc[PT];
-#pragma unroll
-    for (int t = 0; t < PT; ++t) acc[t] = zero;
-    stage_load(0);
-    __syncthreads();               // scales complete
-    const float sx = s_sc[0];
-    stage_store(sx);
-    __syncthreads();
-    const int coff = 16 * j;
-    float yv[PT][4];
-    for (int sl = 0; sl < j; ++sl) {
-      const bool more = sl + 1 < j;
-      if (more) {
-        stage_load(sl + 1);
-      } else {
-#pragma unroll
-        for (int t = 0; t < PT; ++t)
-#pragma unroll
-          for (int r = 0; r < 4; ++r) yv[t][r] = a.buf[(m0 + (wave * PT + t) * 16 + 4 * g + r) * a.ld + coff + p];
-      }
-#pragma unroll
-      for (int st = 0; st < 10; ++st) {
-        const int sign = st / 5, tp = st % 5;
-        const unsigned char* plane = smemh + 2 * sign * PLANE;
-        const d16_h8 Bh = *reinterpret_cast<const d16_h8*>(smw + st * 2048 + lane * 16);
-        const d16_h8 Bl = *reinterpret_cast<const d16_h8*>(smw + st * 2048 + 1024 + lane * 16);
-        const int t0 = 2 * tp, t1 = (2 * tp + 1 < 9) ? 2 * tp + 1 : 8;
-        const int sh0 = ((t0 / 3 - 1) * RS + (t0 % 3 - 1)) * 32;
-        const int sh1 = ((t1 / 3 - 1) * RS + (t1 % 3 - 1)) * 32;
-        const int sh = hiTap ? sh1 : sh0;
-        d16_h8 Ah[PT], Al[PT];
-#pragma unroll
-        for (int t = 0; t < PT; ++t) {
-          const unsigned char* ap = plane + ab[t] + sh;
-          Ah[t] = *reinterpret_cast<const d16_h8*>(ap);
-          Al[t] = *reinterpret_cast<const d16_h8*>(ap + PLANE);
-        }
-#pragma unroll
-        for (int t = 0; t < PT; ++t) acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(Al[t], Bh, acc[t], 0, 0, 0);
-#pragma unroll
-        for (int t = 0; t < PT; ++t) acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(Ah[t], Bl, acc[t], 0, 0, 0);
-#pragma unroll
-        for (int t = 0; t < PT; ++t) acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(Ah[t], Bh, acc[t], 0, 0, 0);
-      }
-      __syncthreads();
-      if (more) {
-        stage_store(sx);
-        __syncthreads();
-      }
-    }
-    const float so = s_sc[1];
-    unsigned omax = 0u;
-#pragma unroll
-    for (int t = 0; t < PT; ++t)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const long m = m0 + (wave * PT + t) * 16 + 4 * g + r;
-        const float o = fmaf(acc[t][r], so, yv[t][r]);
-        a.buf[m * a.ld + coff + p] = o;
-        const unsigned ob = amax_bits(o);
-        omax = ob > omax ? ob : omax;
-      }
-    // the workgroup's own maximum bounds what the next layers read of this slice; the global record for the later consumers
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-      const unsigned w = (unsigned)__shfl_xor((int)omax, o, 64);
-      omax = w > omax ? w : omax;
-    }
-    if (lane == 0) atomicMax(&s_run[0], omax);
-    amax_commit(a.rec + (size_t)(1 + j) * (kAmaxSub * kAmaxSubStride), omax);
-    // (the slice just written is read back by other waves of THIS workgroup in the next trip: the barrier at the top of the loop
-    // orders the stores before those loads -- workgroup scope, the vector cache is shared by the workgroup's waves; an
-    // agent-scope release here would write the whole L2 back once per layer and workgroup)
+    if (ln.tid == 0) h2_set_scales(s_run[0] > s_run[1] ? s_run[0] : s_run[1], wq, s_sc);
+    const unsigned omax = h2_fwd_layer<T>(ln, smemh, s_sc, a.buf, xoff, loff, ab, wq, j, a.buf, a.ld, 16 * j, img_base);
+    h2_chain_commit(s_run, a.rec + (size_t)(1 + j) * (kAmaxSub * kAmaxSubStride), omax, ln.lane);
   }
 }
 
@@ -1116,7 +1065,7 @@ struct BwdH2Args {
   const float* rec1;
   int nrec0, nrec1;
   int nsl;
-  int N, H, W, logW, ldg, ldx, TR, RS;
+  int N, H, W, ldg, ldx;
   float* amax;           // amax record of the sums written, or null
 };
 
@@ -1161,197 +1110,128 @@ __global__ __launch_bounds__(256) void dense16_h2_bwd_prep_kernel(H2BwdPrepArgs 
   }
 }
 
-template <int PT, int WW>
-__global__ __launch_bounds__(256, 2) void dense16_bwd_h2_kernel(BwdH2Args a) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char smemh[];
-  __shared__ float s_sc[2];
-  constexpr int WBYTES = kH2SliceU16 * 2;
-  // the image width is a template parameter: tile rows, LDS row stride and plane size are then compile-time constants and the
-  // plane / piece / tile offsets of the fragment reads fold into the ds_read immediates (one address add per tap pair
-  // instead of one per read: 100 -> 10 per slice)
-  constexpr bool W8 = WW == 8;
-  constexpr int TR = 64 * PT / WW, RS = WW == 8 ? 16 : WW + 2, LOGW = WW == 8 ? 3 : WW == 16 ? 4 : WW == 32 ? 5 : 6;
-  constexpr int PLANE = (TR + 2) * RS * 32;                 // bytes of one (sign, piece) plane
-  constexpr int NIT = ((TR + 2) * WW * 4 + 255) / 256;      // staging passes: (TR + 2) x W pixels x 4 quads over 256 threads
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int p = lane & 15, g = lane >> 4;
-  const int tiles_per_img = a.H / TR;
-  const int n = blockIdx.x / tiles_per_img;
-  const int r0 = (blockIdx.x - n * tiles_per_img) * TR;
-  unsigned char* const smw = smemh + 2 * PLANE;
-  for (int i = tid; i < 2 * PLANE / 16; i += 256) reinterpret_cast<u32x4*>(smemh)[i] = u32x4{0u, 0u, 0u, 0u};
-  if (wave == 0) {
-    unsigned mb = 0u;
-    const int nr = a.nrec0 + a.nrec1;
-    for (int i = lane; i < 16 * nr; i += 64) {
-      const int r = i >> 4;
-      const float* base = r < a.nrec0 ? a.rec0 + (long)r * (kAmaxSub * kAmaxSubStride) : a.rec1 + (long)(r - a.nrec0) * (kAmaxSub * kAmaxSubStride);
-      const unsigned v = reinterpret_cast<const unsigned*>(base)[(i & 15) * kAmaxSubStride];
-      mb = v > mb ? v : mb;
-    }
-    for (int o = 32; o; o >>= 1) {
-      const unsigned t = __shfl_xor(mb, o);
-      mb = t > mb ? t : mb;
-    }
-    if (lane == 0) {
-      const float amax = __uint_as_float(mb);
-      int e = 0;
-      if (amax > 0.f) e = __builtin_amdgcn_frexp_expf(amax);
-      const int ew = *reinterpret_cast<const int*>(a.wq);
-      s_sc[0] = (amax <= 3.0e38f) ? __builtin_ldexpf(1.f, 14 - e) : __builtin_nanf("");
-      s_sc[1] = (amax <= 3.0e38f) ? __builtin_ldexpf(1.f, e + ew - 28) : __builtin_nanf("");
-    }
-  }
-  const int slot = tid & 3;
-  const int total = (TR + 2) * WW * 4;
-  const long img_base = (long)n * a.H * WW;
-  const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
-  long goff[NIT];
-  int loff[NIT];
+// input gradient, one source (gradient) slice out of LDS: 5 tap pairs x 6 MFMAs per pixel tile (the + and - effective channels
+// of the output slice share the gradient fragments)
+template <class T>
+__device__ __forceinline__ void h2_bwd_step(const H2Lane& ln, const unsigned char* smem, const unsigned char* smw, const int (&ab)[T::PT],
+                                            f32x4 (&acc)[2][T::PT]) {
+  constexpr int PT = T::PT;
 #pragma unroll
-  for (int it = 0; it < NIT; ++it) {
-    const int i = it * 256 + tid;
-    const int px = i >> 2;
-    const int row = px >> LOGW, col = px & (WW - 1);
-    const int ir = r0 - 1 + row;
-    const bool ok = i < total && (unsigned)ir < (unsigned)a.H;
-    goff[it] = ok ? (img_base + (long)ir * WW + col) * a.ldg + 4 * slot : -1;
-    loff[it] = i < total ? (row * RS + col + 1) * 32 + slot * 8 : -1;
+  for (int tp = 0; tp < 5; ++tp) {
+    const d16_h8 Bhp = *reinterpret_cast<const d16_h8*>(smw + tp * 2048 + ln.lane * 16);
+    const d16_h8 Blp = *reinterpret_cast<const d16_h8*>(smw + tp * 2048 + 1024 + ln.lane * 16);
+    const d16_h8 Bhn = *reinterpret_cast<const d16_h8*>(smw + (5 + tp) * 2048 + ln.lane * 16);
+    const d16_h8 Bln = *reinterpret_cast<const d16_h8*>(smw + (5 + tp) * 2048 + 1024 + ln.lane * 16);
+    const int sh = h2_tap_shift<T>(ln, tp);
+    d16_h8 Ah[PT], Al[PT];
+#pragma unroll
+    for (int t = 0; t < PT; ++t) {
+      const unsigned char* ap = smem + ab[t] + sh;
+      Ah[t] = *reinterpret_cast<const d16_h8*>(ap);
+      Al[t] = *reinterpret_cast<const d16_h8*>(ap + T::PLANE);
+    }
+#pragma unroll
+    for (int t = 0; t < PT; ++t) {
+      acc[0][t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(Al[t], Bhp, acc[0][t], 0, 0, 0);
+      acc[1][t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(Al[t], Bhn, acc[1][t], 0, 0, 0);
+    }
+#pragma unroll
+    for (int t = 0; t < PT; ++t) {
+      acc[0][t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(Ah[t], Blp, acc[0][t], 0, 0, 0);
+      acc[1][t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(Ah[t], Bln, acc[1][t], 0, 0, 0);
+    }
+#pragma unroll
+    for (int t = 0; t < PT; ++t) {
+      acc[0][t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(Ah[t], Bhp, acc[0][t], 0, 0, 0);
+      acc[1][t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(Ah[t], Bhn, acc[1][t], 0, 0, 0);
+    }
   }
-  f32x4 R[NIT];
+}
+// The gradient of one slice on this workgroup's band: dx += [x > 0] G+ - [x < 0] G- gathered from the nsl gradient slices at
+// g (first channel of the first source slice).  X_UNDER_LAST: fetch x and the old dx under the last slice's matrix work (32
+// more live registers at PT = 4) instead of in the epilogue.  Returns the bits of the largest magnitude this thread wrote.
+template <class T, bool X_UNDER_LAST>
+__device__ __forceinline__ unsigned h2_bwd_layer(const H2Lane& ln, unsigned char* smem, const float* s_sc, const float* g,
+                                                 const long (&goff)[T::NIT], const int (&loff)[T::NIT], const int (&ab)[T::PT],
+                                                 const unsigned char* wq, int nsl, const float* x, int ldx, float* dx, int ldg, long m0) {
+  constexpr int PT = T::PT;
+  unsigned char* const smw = smem + 2 * T::PLANE;
+  const unsigned char* wsrc = wq + kH2HdrBytes + ln.tid * 16;
+  f32x4 R[T::NIT];
   u32x4 WR[5];
-  const unsigned char* wsrc = a.wq + kH2HdrBytes + tid * 16;
-  auto stage_load = [&](int sl) {
-#pragma unroll
-    for (int it = 0; it < NIT; ++it) R[it] = goff[it] >= 0 ? *reinterpret_cast<const f32x4*>(a.g + goff[it] + 16 * sl) : zero;
-#pragma unroll
-    for (int q = 0; q < 5; ++q) WR[q] = *reinterpret_cast<const u32x4*>(wsrc + (long)sl * WBYTES + q * 4096);
-  };
-  auto stage_store = [&](float sd) {
-#pragma unroll
-    for (int it = 0; it < NIT; ++it) {
-      if (loff[it] >= 0) {
-        unsigned wd[2][2];
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-          const d16_f2 v = d16_f2{R[it][2 * h], R[it][2 * h + 1]} * sd;
-          const d16_h2 hi = __builtin_convertvector(v, d16_h2);
-          const d16_h2 lo = __builtin_convertvector(v - __builtin_convertvector(hi, d16_f2), d16_h2);
-          wd[0][h] = __builtin_bit_cast(unsigned, hi);
-          wd[1][h] = __builtin_bit_cast(unsigned, lo);
-        }
-        unsigned char* dst = smemh + loff[it];
-        *reinterpret_cast<u32x2*>(dst) = u32x2{wd[0][0], wd[0][1]};
-        *reinterpret_cast<u32x2*>(dst + PLANE) = u32x2{wd[1][0], wd[1][1]};
-      }
-    }
-#pragma unroll
-    for (int q = 0; q < 5; ++q) *reinterpret_cast<u32x4*>(smw + q * 4096 + tid * 16) = WR[q];
-  };
-  int ab[PT];
-#pragma unroll
-  for (int t = 0; t < PT; ++t) {
-    const int q0 = (wave * PT + t) * 16;
-    int rr, cc;
-    if (W8) {
-      rr = (q0 >> 3) + (p >> 3);
-      cc = p & 7;
-    } else {
-      rr = q0 >> LOGW;
-      cc = (q0 & (WW - 1)) + p;
-    }
-    ab[t] = ((rr + 1) * RS + cc + 1) * 32 + 16 * (g & 1);
-  }
   f32x4 acc[2][PT];
 #pragma unroll
-  for (int t = 0; t < PT; ++t) acc[0][t] = acc[1][t] = zero;
-  const int hiTap = g >> 1;
-  stage_load(0);
+  for (int t = 0; t < PT; ++t) acc[0][t] = acc[1][t] = f32x4{0.f, 0.f, 0.f, 0.f};
+  float xv[PT][4], old[PT][4];
+  auto fetch_x = [&] {
+#pragma unroll
+    for (int t = 0; t < PT; ++t)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const long m = h2_out_pixel<T>(ln, m0, t, r);
+        xv[t][r] = x[m * ldx + ln.p];
+        old[t][r] = dx[m * ldg + ln.p];
+      }
+  };
+  h2_load_slice<T>(g, goff, wsrc, 0, R, WR);
   __syncthreads();
   const float sd = s_sc[0];
-  stage_store(sd);
+  h2_store_plain<T>(smem, loff, R, sd);
+  h2_store_weights(smw, ln.tid, WR);
   __syncthreads();
-  const long m0 = (img_base + (long)r0 * WW);
-  float xv[PT][4], old[PT][4];
-  for (int sl = 0; sl < a.nsl; ++sl) {
-    const bool more = sl + 1 < a.nsl;
-    if (more) {
-      stage_load(sl + 1);
-    } else if (PT < 4) {       // (PT = 4: 32 more live registers would spill; loaded in the epilogue)
-#pragma unroll
-      for (int t = 0; t < PT; ++t)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const long m = m0 + (wave * PT + t) * 16 + 4 * g + r;
-          xv[t][r] = a.x[m * a.ldx + p];
-          old[t][r] = a.dx[m * a.ldg + p];
-        }
-    }
-#pragma unroll
-    for (int tp = 0; tp < 5; ++tp) {
-      const d16_h8 Bhp = *reinterpret_cast<const d16_h8*>(smw + tp * 2048 + lane * 16);
-      const d16_h8 Blp = *reinterpret_cast<const d16_h8*>(smw + tp * 2048 + 1024 + lane * 16);
-      const d16_h8 Bhn = *reinterpret_cast<const d16_h8*>(smw + (5 + tp) * 2048 + lane * 16);
-      const d16_h8 Bln = *reinterpret_cast<const d16_h8*>(smw + (5 + tp) * 2048 + 1024 + lane * 16);
-      const int t0 = 2 * tp, t1 = (2 * tp + 1 < 9) ? 2 * tp + 1 : 8;
-      const int sh0 = ((t0 / 3 - 1) * RS + (t0 % 3 - 1)) * 32;
-      const int sh1 = ((t1 / 3 - 1) * RS + (t1 % 3 - 1)) * 32;
-      const int sh = hiTap ? sh1 : sh0;
-      d16_h8 Ah[PT], Al[PT];
-#pragma unroll
-      for (int t = 0; t < PT; ++t) {
-        const unsigned char* ap = smemh + ab[t] + sh;
-        Ah[t] = *reinterpret_cast<const d16_h8*>(ap);
-        Al[t] = *reinterpret_cast<const d16_h8*>(ap + PLANE);
-      }
-#pragma unroll
-      for (int t = 0; t < PT; ++t) {
-        acc[0][t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(Al[t], Bhp, acc[0][t], 0, 0, 0);
-        acc[1][t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(Al[t], Bhn, acc[1][t], 0, 0, 0);
-      }
-#pragma unroll
-      for (int t = 0; t < PT; ++t) {
-        acc[0][t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(Ah[t], Blp, acc[0][t], 0, 0, 0);
-        acc[1][t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(Ah[t], Bln, acc[1][t], 0, 0, 0);
-      }
-#pragma unroll
-      for (int t = 0; t < PT; ++t) {
-        acc[0][t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(Ah[t], Bhp, acc[0][t], 0, 0, 0);
-        acc[1][t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(Ah[t], Bhn, acc[1][t], 0, 0, 0);
-      }
-    }
+  for (int sl = 0; sl < nsl; ++sl) {
+    const bool more = sl + 1 < nsl;
+    if (more) h2_load_slice<T>(g, goff, wsrc, sl + 1, R, WR);
+    else if (X_UNDER_LAST) fetch_x();
+    h2_bwd_step<T>(ln, smem, smw, ab, acc);
     __syncthreads();
     if (more) {
-      stage_store(sd);
+      h2_store_plain<T>(smem, loff, R, sd);
+      h2_store_weights(smw, ln.tid, WR);
       __syncthreads();
     }
   }
   const float so = s_sc[1];
   unsigned omax = 0u;
-  if (PT >= 4) {
-#pragma unroll
-    for (int t = 0; t < PT; ++t)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const long m = m0 + (wave * PT + t) * 16 + 4 * g + r;
-        xv[t][r] = a.x[m * a.ldx + p];
-        old[t][r] = a.dx[m * a.ldg + p];
-      }
-  }
+  if (!X_UNDER_LAST) fetch_x();
 #pragma unroll
   for (int t = 0; t < PT; ++t)
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
-      const long m = m0 + (wave * PT + t) * 16 + 4 * g + r;
       const float xq = xv[t][r];
       float o = old[t][r];
       // (a NaN scale must stay loud whatever the sign of x: add the sums, masked by a factor)
       o = fmaf(acc[0][t][r] * so, xq > 0.f ? 1.f : 0.f, o);
       o = fmaf(acc[1][t][r] * so, xq < 0.f ? -1.f : 0.f, o);
-      a.dx[m * a.ldg + p] = o;
+      dx[h2_out_pixel<T>(ln, m0, t, r) * ldg + ln.p] = o;
       const unsigned ob = amax_bits(o);
       omax = ob > omax ? ob : omax;
     }
+  return omax;
+}
+
+template <int PT, int WW>
+__global__ __launch_bounds__(256, 2) void dense16_bwd_h2_kernel(BwdH2Args a) {
+  using T = H2Tile<PT, WW>;
+  extern __shared__ __attribute__((aligned(16))) unsigned char smemh[];
+  __shared__ float s_sc[2];
+  const H2Lane ln;
+  const int tiles_per_img = a.H / T::TR;
+  const int n = blockIdx.x / tiles_per_img;
+  const int r0 = (blockIdx.x - n * tiles_per_img) * T::TR;
+  h2_zero_planes<T, 2>(smemh, ln.tid);
+  if (ln.wave == 0) {
+    const unsigned mb = h2_records_max(a.rec0, a.nrec0, a.rec1, a.nrec1, ln.lane);
+    if (ln.lane == 0) h2_set_scales(mb, a.wq, s_sc);
+  }
+  const long img_base = (long)n * a.H * WW;
+  long goff[T::NIT];
+  int loff[T::NIT], ab[PT];
+  h2_stage_offsets<T>(ln.tid, img_base, r0, a.H, a.ldg, goff, loff);
+  h2_frag_bases<T>(ln, ab);
+  // (PT = 4: x and the old dx live under the last slice would spill; loaded in the epilogue)
+  const unsigned omax = h2_bwd_layer<T, (PT < 4)>(ln, smemh, s_sc, a.g, goff, loff, ab, a.wq, a.nsl, a.x, a.ldx, a.dx, a.ldg,
+                                                  img_base + (long)r0 * WW);
   if (a.amax) amax_commit(a.amax, omax);
 }
 
@@ -1371,182 +1251,30 @@ struct ChainBwdH2Args {
 };
 template <int PT, int WW>
 __global__ __launch_bounds__(256, 2) void dense16_chain_bwd_h2_kernel(ChainBwdH2Args a) {
+  using T = H2Tile<PT, WW>;
   extern __shared__ __attribute__((aligned(16))) unsigned char smemh[];
   __shared__ float s_sc[2];
   __shared__ unsigned s_run[2];
-  constexpr int NIT = PT + 1;
-  constexpr int WBYTES = kH2SliceU16 * 2;
-  constexpr bool W8 = WW == 8;
-  constexpr int TR = 64 * PT / WW, RS = WW == 8 ? 16 : WW + 2, LOGW = WW == 8 ? 3 : WW == 16 ? 4 : 5;
-  constexpr int PLANE = (TR + 2) * RS * 32;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int p = lane & 15, g = lane >> 4;
+  const H2Lane ln;
   const int n = blockIdx.x;
-  unsigned char* const smw = smemh + 2 * PLANE;
-  for (int i = tid; i < 2 * PLANE / 16; i += 256) reinterpret_cast<u32x4*>(smemh)[i] = u32x4{0u, 0u, 0u, 0u};
-  if (wave == 0) {
-    unsigned mb = 0u;
-    for (int i = lane; i < 16 * 2; i += 64) {
-      const float* base = (i >> 4) == 0 ? a.rec0 : a.slice_rec + (long)(a.nslices - 1) * (kAmaxSub * kAmaxSubStride);
-      const unsigned v = reinterpret_cast<const unsigned*>(base)[(i & 15) * kAmaxSubStride];
-      mb = v > mb ? v : mb;
-    }
-    for (int o = 32; o; o >>= 1) {
-      const unsigned t = __shfl_xor(mb, o);
-      mb = t > mb ? t : mb;
-    }
-    if (lane == 0) { s_run[0] = 0u; s_run[1] = mb; }
+  h2_zero_planes<T, 2>(smemh, ln.tid);
+  if (ln.wave == 0) {
+    const unsigned mb = h2_records_max(a.rec0, 1, a.slice_rec + (long)(a.nslices - 1) * (kAmaxSub * kAmaxSubStride), 1, ln.lane);
+    if (ln.lane == 0) { s_run[0] = 0u; s_run[1] = mb; }
   }
-  const int slot = tid & 3;
-  const int total = (TR + 2) * WW * 4;
   const long img_base = (long)n * a.H * WW;
-  const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
-  long goff[NIT];
-  int loff[NIT];
-#pragma unroll
-  for (int it = 0; it < NIT; ++it) {
-    const int i = it * 256 + tid;
-    const int px = i >> 2;
-    const int row = px >> LOGW, col = px & (WW - 1);
-    const int ir = row - 1;
-    const bool ok = i < total && (unsigned)ir < (unsigned)a.H;
-    goff[it] = ok ? (img_base + (long)ir * WW + col) * a.ldg + 4 * slot : -1;
-    loff[it] = i < total ? (row * RS + col + 1) * 32 + slot * 8 : -1;
-  }
-  int ab[PT];
-#pragma unroll
-  for (int t = 0; t < PT; ++t) {
-    const int q0 = (wave * PT + t) * 16;
-    int rr, cc;
-    if (W8) {
-      rr = (q0 >> 3) + (p >> 3);
-      cc = p & 7;
-    } else {
-      rr = q0 >> LOGW;
-      cc = (q0 & (WW - 1)) + p;
-    }
-    ab[t] = ((rr + 1) * RS + cc + 1) * 32 + 16 * (g & 1);
-  }
-  const int hiTap = g >> 1;
-  const long m0 = img_base;
+  long goff[T::NIT];
+  int loff[T::NIT], ab[PT];
+  h2_stage_offsets<T>(ln.tid, img_base, 0, a.H, a.ldg, goff, loff);
+  h2_frag_bases<T>(ln, ab);
   for (int c = a.nslices - 2; c >= 0; --c) {
-    const int nsl = a.nslices - 1 - c;
     const unsigned char* const wq = a.wq[c];
-    const float* const gsrc = a.g + 16 * (c + 1);
-    float* const dx = a.g + 16 * c;
-    const float* const xc = a.x + 16 * c;
     __syncthreads();
-    if (tid == 0) {
-      const unsigned mb = s_run[0] > s_run[1] ? s_run[0] : s_run[1];
-      const float amax = __uint_as_float(mb);
-      int e = 0;
-      if (amax > 0.f) e = __builtin_amdgcn_frexp_expf(amax);
-      const int ew = *reinterpret_cast<const int*>(wq);
-      s_sc[0] = (amax <= 3.0e38f) ? __builtin_ldexpf(1.f, 14 - e) : __builtin_nanf("");
-      s_sc[1] = (amax <= 3.0e38f) ? __builtin_ldexpf(1.f, e + ew - 28) : __builtin_nanf("");
-    }
-    f32x4 R[NIT];
-    u32x4 WR[5];
-    const unsigned char* wsrc = wq + kH2HdrBytes + tid * 16;
-    auto stage_load = [&](int sl) {
-#pragma unroll
-      for (int it = 0; it < NIT; ++it) R[it] = goff[it] >= 0 ? *reinterpret_cast<const f32x4*>(gsrc + goff[it] + 16 * sl) : zero;
-#pragma unroll
-      for (int q = 0; q < 5; ++q) WR[q] = *reinterpret_cast<const u32x4*>(wsrc + (long)sl * WBYTES + q * 4096);
-    };
-    auto stage_store = [&](float sd) {
-#pragma unroll
-      for (int it = 0; it < NIT; ++it) {
-        if (loff[it] >= 0) {
-          unsigned wd[2][2];
-#pragma unroll
-          for (int h = 0; h < 2; ++h) {
-            const d16_f2 v = d16_f2{R[it][2 * h], R[it][2 * h + 1]} * sd;
-            const d16_h2 hi = __builtin_convertvector(v, d16_h2);
-            const d16_h2 lo = __builtin_convertvector(v - __builtin_convertvector(hi, d16_f2), d16_h2);
-            wd[0][h] = __builtin_bit_cast(unsigned, hi);
-            wd[1][h] = __builtin_bit_cast(unsigned, lo);
-          }
-          unsigned char* dst = smemh + loff[it];
-          *reinterpret_cast<u32x2*>(dst) = u32x2{wd[0][0], wd[0][1]};
-          *reinterpret_cast<u32x2*>(dst + PLANE) = u32x2{wd[1][0], wd[1][1]};
-        }
-      }
-#pragma unroll
-      for (int q = 0; q < 5; ++q) *reinterpret_cast<u32x4*>(smw + q * 4096 + tid * 16) = WR[q];
-    };
-    f32x4 acc[2][PT];
-#pragma unroll
-    for (int t = 0; t < PT; ++t) acc[0][t] = acc[1][t] = zero;
-    stage_load(0);
-    __syncthreads();
-    const float sd = s_sc[0];
-    stage_store(sd);
-    __syncthreads();
-    for (int sl = 0; sl < nsl; ++sl) {
-      const bool more = sl + 1 < nsl;
-      if (more) stage_load(sl + 1);
-#pragma unroll
-      for (int tp = 0; tp < 5; ++tp) {
-        const d16_h8 Bhp = *reinterpret_cast<const d16_h8*>(smw + tp * 2048 + lane * 16);
-        const d16_h8 Blp = *reinterpret_cast<const d16_h8*>(smw + tp * 2048 + 1024 + lane * 16);
-        const d16_h8 Bhn = *reinterpret_cast<const d16_h8*>(smw + (5 + tp) * 2048 + lane * 16);
-        const d16_h8 Bln = *reinterpret_cast<const d16_h8*>(smw + (5 + tp) * 2048 + 1024 + lane * 16);
-        const int t0 = 2 * tp, t1 = (2 * tp + 1 < 9) ? 2 * tp + 1 : 8;
-        const int sh0 = ((t0 / 3 - 1) * RS + (t0 % 3 - 1)) * 32;
-        const int sh1 = ((t1 / 3 - 1) * RS + (t1 % 3 - 1)) * 32;
-        const int sh = hiTap ? sh1 : sh0;
-        d16_h8 Ah[PT], Al[PT];
-#pragma unroll
-        for (int t = 0; t < PT; ++t) {
-          const unsigned char* ap = smemh + ab[t] + sh;
-          Ah[t] = *reinterpret_cast<const d16_h8*>(ap);
-          Al[t] = *reinterpret_cast<const d16_h8*>(ap + PLANE);
-        }
-#pragma unroll
-        for (int t = 0; t < PT; ++t) {
-          acc[0][t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(Al[t], Bhp, acc[0][t], 0, 0, 0);
-          acc[1][t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(Al[t], Bhn, acc[1][t], 0, 0, 0);
-        }
-#pragma unroll
-        for (int t = 0; t < PT; ++t) {
-          acc[0][t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(Ah[t], Blp, acc[0][t], 0, 0, 0);
-          acc[1][t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(Ah[t], Bln, acc[1][t], 0, 0, 0);
-        }
-#pragma unroll
-        for (int t = 0; t < PT; ++t) {
-          acc[0][t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(Ah[t], Bhp, acc[0][t], 0, 0, 0);
-          acc[1][t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(Ah[t], Bhn, acc[1][t], 0, 0, 0);
-        }
-      }
-      __syncthreads();
-      if (more) {
-        stage_store(sd);
-        __syncthreads();
-      }
-    }
-    const float so = s_sc[1];
-    unsigned omax = 0u;
-#pragma unroll
-    for (int t = 0; t < PT; ++t)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const long m = m0 + (wave * PT + t) * 16 + 4 * g + r;
-        const float xq = xc[m * a.ldx + p];
-        float o = dx[m * a.ldg + p];
-        o = fmaf(acc[0][t][r] * so, xq > 0.f ? 1.f : 0.f, o);
-        o = fmaf(acc[1][t][r] * so, xq < 0.f ? -1.f : 0.f, o);
-        dx[m * a.ldg + p] = o;
-        const unsigned ob = amax_bits(o);
-        omax = ob > omax ? ob : omax;
-      }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-      const unsigned w = (unsigned)__shfl_xor((int)omax, o, 64);
-      omax = w > omax ? w : omax;
-    }
-    if (lane == 0) atomicMax(&s_run[0], omax);
-    amax_commit(a.slice_rec + (size_t)c * (kAmaxSub * kAmaxSubStride), omax);
+    if (ln.tid == 0) h2_set_scales(s_run[0] > s_run[1] ? s_run[0] : s_run[1], wq, s_sc);
+    // (x and the old dx in the epilogue for every PT)
+    const unsigned omax = h2_bwd_layer<T, false>(ln, smemh, s_sc, a.g + 16 * (c + 1), goff, loff, ab, wq, a.nslices - 1 - c, a.x + 16 * c,
+                                                 a.ldx, a.g + 16 * c, a.ldg, img_base);
+    h2_chain_commit(s_run, a.slice_rec + (size_t)c * (kAmaxSub * kAmaxSubStride), omax, ln.lane);
   }
 }
 
@@ -1987,9 +1715,34 @@ int ilog2i(int v) {
   return l;
 }
 
-}  // namespace
+// Block tile of the LDS kernels: TR full rows = 64 PT pixels of one image (16 per wave and pixel tile), LDS row stride RS.
+// (fp16 x 2 growth kernels: half-height tiles -- three workgroups per compute unit at 32 x 32 -- measured 4 % slower in round 4)
+struct D16Tile {
+  int PT, TR, RS;
+};
+D16Tile d16_tile(int N, int H, int W) {
+  int PT = H * W >= 256 ? 4 : H * W / 64;
+  while (PT > 1 && (long)N * H * W / (64 * PT) < 512) PT >>= 1;
+  return D16Tile{PT, 64 * PT / W, W == 8 ? 16 : W + 2};
+}
 
-bool dense16_enabled() { return true; }
+// f(PT, W) as compile-time constants for the instantiations of the fp16 x 2 kernels: W 16 / 32 / 64 x PT 1 / 2 / 4, W 8 x PT 1
+// (dense16_h2_shape_ok admits nothing else)
+template <class F>
+void h2_dispatch(int PT, int W, F&& f) {
+  using std::integral_constant;
+  auto with_w = [&](auto w) {
+    if (PT == 4) f(integral_constant<int, 4>{}, w);
+    else if (PT == 2) f(integral_constant<int, 2>{}, w);
+    else f(integral_constant<int, 1>{}, w);
+  };
+  if (W == 64) with_w(integral_constant<int, 64>{});
+  else if (W == 32) with_w(integral_constant<int, 32>{});
+  else if (W == 16) with_w(integral_constant<int, 16>{});
+  else f(integral_constant<int, 1>{}, integral_constant<int, 8>{});
+}
+
+}  // namespace
 
 int dense16_fwd(const Dense16Geo& g, const float* x, const float* wT, const float* bias, float* y,
                 int ldy, int coff, int accumulate, hipStream_t s, float* amax_out) {
@@ -2003,16 +1756,16 @@ int dense16_fwd(const Dense16Geo& g, const float* x, const float* wT, const floa
   a.K = 9 * g.Ceff; a.ldy = ldy; a.coff = coff;
   if (g.W >= 8 && g.W <= 64 && g.H * g.W >= 64) {
     // haloed LDS tile: block = TR full rows = 64*PT pixels of one image
-    int PT = g.H * g.W >= 256 ? 4 : g.H * g.W / 64;
-    while (PT > 1 && (long)g.N * g.H * g.W / (64 * PT) < 512) PT >>= 1;
+    const D16Tile t = d16_tile(g.N, g.H, g.W);
+    const int PT = t.PT;
     FwdLdsArgs l;
     l.accumulate = accumulate;
     l.amax = amax_out;
     l.x = x; l.cmap = g.cmap; l.wT = wT; l.bias = bias; l.y = y;
     l.N = g.N; l.H = g.H; l.W = g.W; l.logW = ilog2i(g.W); l.ldx = g.ldx; l.C = g.C; l.Ceff = g.Ceff;
     l.doubled = g.doubled; l.K = 9 * g.Ceff; l.ldy = ldy; l.coff = coff;
-    l.TR = 64 * PT / g.W;
-    l.RS = g.W == 8 ? 16 : g.W + 2;
+    l.TR = t.TR;
+    l.RS = t.RS;
     if (l.TR >= 1 && g.H % l.TR == 0) {
       const size_t lds = (size_t)(l.TR + 2) * l.RS * kPixQuads * 16;
       const dim3 grid(g.N * (g.H / l.TR)), blk(256);
@@ -2052,20 +1805,12 @@ int dense16_fwd(const Dense16Geo& g, const float* x, const float* wT, const floa
   return OTGAN_OK;
 }
 
-// pixel tiles of 16 per wave (workgroup = 64 PT pixels = full rows) of the fp16 x 2 growth kernels (half-height tiles --
-// three workgroups per compute unit at 32 x 32 -- measured 4 % slower in round 4)
-static int h2_pt(int N, int H, int W) {
-  int PT = H * W >= 256 ? 4 : H * W / 64;
-  while (PT > 1 && (long)N * H * W / (64 * PT) < 512) PT >>= 1;
-  return PT;
-}
 size_t dense16_h2_filter_bytes(int nsl) { return nsl > 0 ? (size_t)kH2HdrBytes + (size_t)nsl * kH2SliceU16 * 2 : 0; }
 
 bool dense16_h2_shape_ok(int N, int H, int W) {
   if (!(W == 8 || W == 16 || W == 32 || W == 64) || H * W < 64) return false;
-  const int PT = h2_pt(N, H, W);
-  const int TR = 64 * PT / W;
-  return TR >= 1 && H % TR == 0 && (W != 8 || PT == 1);   // (8-wide images: only the one-tile instantiation exists)
+  const D16Tile t = d16_tile(N, H, W);
+  return t.TR >= 1 && H % t.TR == 0 && (W != 8 || t.PT == 1);   // (8-wide images: only the one-tile instantiation exists)
 }
 
 int dense16_h2_prepare(const float* const* wT, const int* nsl, void* const* out, int count, hipStream_t s) {
@@ -2078,20 +1823,17 @@ int dense16_h2_prepare(const float* const* wT, const int* nsl, void* const* out,
 
 int dense16_fwd_h2(int N, int H, int W, int nsl, const float* x, int ldx, const void* wq, const float* rec, int nrec,
                    float* y, int ldy, int coff, hipStream_t s, float* amax_out) {
-  const int PT = h2_pt(N, H, W);
+  const D16Tile t = d16_tile(N, H, W);
   FwdH2Args a;
   a.x = x; a.wq = (const unsigned char*)wq; a.y = y; a.rec = rec; a.nrec = nrec; a.nsl = nsl;
-  a.N = N; a.H = H; a.W = W; a.logW = ilog2i(W); a.ldx = ldx; a.ldy = ldy; a.coff = coff;
-  a.TR = 64 * PT / W;
-  a.RS = W == 8 ? 16 : W + 2;
+  a.N = N; a.H = H; a.W = W; a.ldx = ldx; a.ldy = ldy; a.coff = coff;
   a.amax = amax_out;
-  const size_t lds = (size_t)4 * (a.TR + 2) * a.RS * 32 + (size_t)kH2SliceU16 * 2;
-  const dim3 grid(N * (H / a.TR)), blk(256);
-  const bool w8 = W == 8;
-#define D16_H2(PT_, W_) hipLaunchKernelGGL((dense16_fwd_h2_kernel<PT_, W_>), grid, blk, lds, s, a)
-  (void)w8;
-  if (W == 64) {
-    if (PT == 4) {
+  const size_t lds = (size_t)4 * (t.TR + 2) * t.RS * 32 + (size_t)kH2SliceU16 * 2;
+  const dim3 grid(N * (H / t.TR)), blk(256);
+  int rc = OTGAN_OK;
+  h2_dispatch(t.PT, W, [&](auto pt, auto w) {
+    constexpr int PT_ = decltype(pt)::value, W_ = decltype(w)::value;
+    if constexpr (PT_ == 4 && W_ == 64) {
       // 69.5 KB of LDS (four planes of 6 x 66 pixels + the slice's weights): above the 64 KB default of dynamic shared memory;
       // two workgroups per compute unit still fit the 160 KB, as at 32 x 32
       static const bool once = [] {
@@ -2099,49 +1841,46 @@ int dense16_fwd_h2(int N, int H, int W, int nsl, const float* x, int ldx, const 
       }();
       if (!once) {
         otgan_set_error("dense16 fwd h2: the 64-wide four-row tile needs 69.5 KB of dynamic shared memory");
-        return OTGAN_ERR_UNSUPPORTED;
+        rc = OTGAN_ERR_UNSUPPORTED;
+        return;
       }
-      D16_H2(4, 64);
-    } else if (PT == 2) D16_H2(2, 64);
-    else D16_H2(1, 64);
-  }
-  else if (W == 32) { if (PT == 4) D16_H2(4, 32); else if (PT == 2) D16_H2(2, 32); else D16_H2(1, 32); }
-  else if (W == 16) { if (PT == 4) D16_H2(4, 16); else if (PT == 2) D16_H2(2, 16); else D16_H2(1, 16); }
-  else D16_H2(1, 8);
-#undef D16_H2
-  return OTGAN_OK;
+    }
+    hipLaunchKernelGGL((dense16_fwd_h2_kernel<PT_, W_>), grid, blk, lds, s, a);
+  });
+  return rc;
 }
 
-bool dense16_chain_bwd_h2(int N, int H, int W, int nslices, float* g, int ldg, const float* x, int ldx,
+// Which chains run as ONE launch (a workgroup covers an image), decided here and nowhere else.  Forward: 8 x 8 (PT = 1) and
+// 16 x 16 (PT = 4).  Input gradient: 8 x 8 only -- at 16 x 16 one workgroup per image (256 of them, PT = 4) measured 124.6 us per
+// chain against 7 x 15.3 us for the per-slice kernels on half images (512 workgroups, PT = 2) --
+// profiles/r06_pmc_kernels_densenet.txt; 8 x 8: 45.6 against 64 us
+bool dense16_chain_fwd_h2_takes(int H, int W, int nslices) { return H == W && (W == 8 || W == 16) && nslices >= 2 && nslices <= 17; }
+bool dense16_chain_bwd_h2_takes(int H, int W, int nslices) { return H == W && W == 8 && nslices >= 2 && nslices <= 17; }
+
+void dense16_chain_bwd_h2(int N, int H, int W, int nslices, float* g, int ldg, const float* x, int ldx,
                           const void* const* filters, const float* rec0, float* slice_records, hipStream_t s) {
-  // 8 x 8 only: at 16 x 16 one workgroup per image (256 of them, PT = 4) measured 124.6 us per chain against 7 x 15.3 us for the
-  // per-slice kernels on half images (512 workgroups, PT = 2) -- profiles/r06_pmc_kernels_densenet.txt; 8 x 8: 45.6 against 64 us
-  if (!(H == W && W == 8) || nslices < 2 || nslices > 17) return false;
   ChainBwdH2Args a;
   memset(&a, 0, sizeof(a));
   a.g = g; a.x = x; a.rec0 = rec0; a.slice_rec = slice_records; a.nslices = nslices;
   a.N = N; a.H = H; a.W = W; a.ldg = ldg; a.ldx = ldx;
   for (int c = 0; c + 1 < nslices; ++c) a.wq[c] = (const unsigned char*)filters[c];
-  const int TR = H, RS = W == 8 ? 16 : W + 2;
-  const size_t lds = (size_t)2 * (TR + 2) * RS * 32 + (size_t)kH2SliceU16 * 2;
-  if (W == 8) hipLaunchKernelGGL((dense16_chain_bwd_h2_kernel<1, 8>), dim3(N), dim3(256), lds, s, a);
-  else hipLaunchKernelGGL((dense16_chain_bwd_h2_kernel<4, 16>), dim3(N), dim3(256), lds, s, a);
-  return true;
+  using T = H2Tile<1, 8>;
+  const size_t lds = (size_t)2 * T::PLANE + T::WBYTES;
+  hipLaunchKernelGGL((dense16_chain_bwd_h2_kernel<1, 8>), dim3(N), dim3(256), lds, s, a);
 }
-// the whole chain of a group in ONE launch where a workgroup covers an image (dense16_chain_fwd_h2_kernel); false: not this shape
-bool dense16_chain_fwd_h2(int N, int H, int W, int nslices, float* buf, int ld, const void* const* filters, float* records,
+void dense16_chain_fwd_h2(int N, int H, int W, int nslices, float* buf, int ld, const void* const* filters, float* records,
                           hipStream_t s) {
-  if (!(H == W && (W == 8 || W == 16)) || nslices < 2 || nslices > 17) return false;
   ChainH2Args a;
   memset(&a, 0, sizeof(a));
   a.buf = buf; a.rec = records; a.nslices = nslices; a.N = N; a.H = H; a.W = W; a.ld = ld;
   for (int j = 1; j < nslices; ++j) a.wq[j - 1] = (const unsigned char*)filters[j - 1];
-  const int PT = W == 8 ? 1 : 4, TR = H, RS = W == 8 ? 16 : W + 2;
-  const size_t lds = (size_t)4 * (TR + 2) * RS * 32 + (size_t)kH2SliceU16 * 2;
-  if (W == 8) hipLaunchKernelGGL((dense16_chain_fwd_h2_kernel<1, 8>), dim3(N), dim3(256), lds, s, a);       // 40 KB of LDS
-  else hipLaunchKernelGGL((dense16_chain_fwd_h2_kernel<4, 16>), dim3(N), dim3(256), lds, s, a);             // 61 KB
-  (void)PT;
-  return true;
+  auto launch = [&](auto pt, auto w) {
+    using T = H2Tile<decltype(pt)::value, decltype(w)::value>;
+    const size_t lds = (size_t)4 * T::PLANE + T::WBYTES;
+    hipLaunchKernelGGL((dense16_chain_fwd_h2_kernel<T::PT, T::WW>), dim3(N), dim3(256), lds, s, a);
+  };
+  if (W == 8) launch(std::integral_constant<int, 1>{}, std::integral_constant<int, 8>{});       // 40 KB of LDS
+  else launch(std::integral_constant<int, 4>{}, std::integral_constant<int, 16>{});             // 61 KB
 }
 
 size_t dense16_h2_bwd_filter_bytes(int nsl) { return dense16_h2_filter_bytes(nsl); }
@@ -2167,24 +1906,17 @@ int dense16_h2_bwd_prepare(const Dense16BwdPair* pairs, int npairs, const void* 
 
 int dense16_bwd_h2(int N, int H, int W, int nsl, const float* g, int ldg, const void* wq, const float* x, int ldx, float* dx,
                    const float* rec0, int nrec0, const float* rec1, int nrec1, hipStream_t s, float* amax_out) {
-  const int PT = h2_pt(N, H, W);
+  const D16Tile t = d16_tile(N, H, W);
   BwdH2Args a;
   a.g = g; a.wq = (const unsigned char*)wq; a.x = x; a.dx = dx;
   a.rec0 = rec0; a.rec1 = rec1 ? rec1 : rec0; a.nrec0 = nrec0; a.nrec1 = rec1 ? nrec1 : 0; a.nsl = nsl;
-  a.N = N; a.H = H; a.W = W; a.logW = ilog2i(W); a.ldg = ldg; a.ldx = ldx;
-  a.TR = 64 * PT / W;
-  a.RS = W == 8 ? 16 : W + 2;
+  a.N = N; a.H = H; a.W = W; a.ldg = ldg; a.ldx = ldx;
   a.amax = amax_out;
-  const size_t lds = (size_t)2 * (a.TR + 2) * a.RS * 32 + (size_t)kH2SliceU16 * 2;
-  const dim3 grid(N * (H / a.TR)), blk(256);
-  const bool w8 = W == 8;
-#define D16_B2(PT_, W_) hipLaunchKernelGGL((dense16_bwd_h2_kernel<PT_, W_>), grid, blk, lds, s, a)
-  (void)w8;
-  if (W == 64) { if (PT == 4) D16_B2(4, 64); else if (PT == 2) D16_B2(2, 64); else D16_B2(1, 64); }      // at most 44.75 KB of LDS
-  else if (W == 32) { if (PT == 4) D16_B2(4, 32); else if (PT == 2) D16_B2(2, 32); else D16_B2(1, 32); }
-  else if (W == 16) { if (PT == 4) D16_B2(4, 16); else if (PT == 2) D16_B2(2, 16); else D16_B2(1, 16); }
-  else D16_B2(1, 8);
-#undef D16_B2
+  const size_t lds = (size_t)2 * (t.TR + 2) * t.RS * 32 + (size_t)kH2SliceU16 * 2;      // at most 44.75 KB
+  const dim3 grid(N * (H / t.TR)), blk(256);
+  h2_dispatch(t.PT, W, [&](auto pt, auto w) {
+    hipLaunchKernelGGL((dense16_bwd_h2_kernel<decltype(pt)::value, decltype(w)::value>), grid, blk, lds, s, a);
+  });
   return OTGAN_OK;
 }
 
@@ -2192,12 +1924,11 @@ Dense16Tiling dense16_tiling(int N, int H, int W, int Ceff) {
   Dense16Tiling t;
   memset(&t, 0, sizeof(t));
   if (!(W >= 8 && W <= 64 && H * W >= 64)) return t;
-  int PT = H * W >= 256 ? 4 : H * W / 64;
-  while (PT > 1 && (long)N * H * W / (64 * PT) < 512) PT >>= 1;
-  t.PT = PT;
-  t.TR = 64 * PT / W;
+  const D16Tile tile = d16_tile(N, H, W);
+  t.PT = tile.PT;
+  t.TR = tile.TR;
   if (t.TR < 1 || H % t.TR) return t;
-  t.RS = W == 8 ? 16 : W + 2;
+  t.RS = tile.RS;
   t.tiles = N * (H / t.TR);
   t.nchunk = (Ceff + 31) / 32;
   // workgroups of the weight-gradient grid (pixel splits x channel chunks).  1536 until round 4 (three rounds of the 512

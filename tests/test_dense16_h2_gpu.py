@@ -8,6 +8,8 @@ import numpy as np
 import pytest
 import torch
 
+from tests import dense16_ref as D16
+
 pytestmark = pytest.mark.gpu
 
 
@@ -22,16 +24,14 @@ def dev():
 def _reference(xs, wT, y0):
     """xs [N,H,W,16 n] fp64 (the slices), wT [16, 9 * 32 n]; returns y0 + conv3x3_same(crelu-interleaved xs)."""
     n = xs.shape[-1] // 16
-    parts = []
-    for s in range(n):
-        sl = xs[..., 16 * s:16 * s + 16]
-        parts += [sl.clamp(min=0), (-sl).clamp(min=0)]
-    eff = torch.cat(parts, -1).permute(0, 3, 1, 2)                      # [N, 32 n, H, W]
+    eff = D16.crelu_slices(xs)                                          # [N, 32 n, H, W]
     w = wT.reshape(16, 9, 32 * n).permute(0, 2, 1).reshape(16, 32 * n, 3, 3)
     return y0 + torch.nn.functional.conv2d(eff, w, padding=1).permute(0, 2, 3, 1)
 
 
-@pytest.mark.parametrize("N,H,n_own", [(8, 32, 1), (8, 32, 3), (128, 32, 7), (32, 16, 4), (256, 16, 2), (64, 8, 5), (512, 8, 3)])
+# (64, 32, 2): the two-row tile at 32 x 32, dense16_fwd_h2_kernel<2, 32>; (512, 16, 1): a whole 16 x 16 image per workgroup, <4, 16>
+@pytest.mark.parametrize("N,H,n_own", [(8, 32, 1), (8, 32, 3), (128, 32, 7), (32, 16, 4), (256, 16, 2), (64, 8, 5), (512, 8, 3),
+                                       (64, 32, 2), (512, 16, 1)])
 def test_chain_kernel_vs_fp64(dev, N, H, n_own):
     from otgan_amd import _lib, ops
     from otgan_amd._lib_layers import ConvDesc
@@ -129,6 +129,74 @@ def test_whole_chain_in_one_launch(dev, N, H, nslices):
         a, b = got[..., C0 + 16 * j:C0 + 16 * j + 16].double(), ref[..., C0 + 16 * j:C0 + 16 * j + 16]
         assert float((a - b).norm() / b.norm()) < 2e-5, j
         assert float(R[1 + j].max()) == float(got[..., C0 + 16 * j:C0 + 16 * j + 16].abs().max()), j
+
+
+# one instantiation of dense16_bwd_h2_kernel<PT, W> each, below the 64-wide ones of tests/test_densenet64_gpu.py:
+# <1, 8>, <1, 16>, <2, 16>, <4, 16>, <1, 32>, <2, 32>, <4, 32> (the tile grows with N H W / 64 >= 512 PT)
+@pytest.mark.parametrize("N,H,npairs", [(64, 8, 3), (32, 16, 2), (256, 16, 2), (512, 16, 2), (8, 32, 3), (64, 32, 2), (128, 32, 2)])
+def test_growth_backward_by_slice_vs_fp64(dev, N, H, npairs):
+    """otgan_dense16_bwd_slice_f32 at 8 x 8, 16 x 16 and 32 x 32: the checks of test_growth_backward_by_slice_64_vs_fp64
+    (tests/test_densenet64_gpu.py) at the same bound."""
+    D16.growth_backward_by_slice(dev, N, H, npairs, 2e-5)
+
+
+@pytest.mark.parametrize("N,nslices", [(64, 8), (37, 3), (64, 17)], ids=["block3_group", "odd_batch", "longest"])
+@pytest.mark.parametrize("H", [8, 16], ids=["8x8_one_launch", "16x16_per_slice"])
+def test_whole_backward_chain_vs_fp64(dev, H, N, nslices):
+    """otgan_dense16_chain_bwd_f32 walks a group's slices last to first: slice c gathers [x_c > 0] G+ - [x_c < 0] G- from the
+    (final) gradients of the later slices -- in ONE launch at 8 x 8 (dense16_chain_bwd_h2_kernel, every workgroup bounding the
+    slices written in the launch by what IT wrote), slice by slice at 16 x 16.  Reference: fp64 autograd through the chain
+    (layer j adds conv3x3(crelu(slices < j)) onto slice j) of sum_j <G_j, slice_j> with respect to the slices' initial values,
+    at the forward values in X.  Per slice at the layer tolerance of the suite, 2e-5 relative L2; twice, bit for bit; nothing
+    outside slices 0 .. nslices - 2 of the group written; slice_records[c] holds the amax of slice c as written; and the
+    library's profiler counts the launches of the path meant: one at 8 x 8, one per slice at 16 x 16."""
+    from otgan_amd import _lib, ops
+    L = _lib.lib()
+    g = torch.Generator().manual_seed(1000 + N + H + nslices)
+    F, C0 = 16, 32
+    Ctot = C0 + nslices * F + 16
+    X = torch.randn(N, H, H, Ctot, generator=g)
+    G0 = torch.randn(N, H, H, Ctot, generator=g)
+    for t in (X, G0):
+        t[..., C0 + F:C0 + 2 * F] *= 11.0                                 # slices of different magnitudes
+        t[3 % N] *= 7.0                                                   # ... and images
+    X[X == 0] = 1.0                                                       # (the derivative of CReLU at an exact zero is a convention)
+    ws = [(torch.randn(9, 2 * F * k, F, generator=g) * (0.05 / k ** 0.5)) for k in range(1, nslices)]
+    grp = slice(C0, C0 + nslices * F)
+    want = D16.chain_backward_reference(X[..., grp].double(), G0[..., grp].double(), ws)
+    wd, fwd, pf = D16.prepare_filters(L, _lib, ws, dev)
+    bqs = [D16.prepare_bwd_filters(L, _lib, wd, fwd, pf, c, dev) for c in range(nslices - 1)]
+    pb = (ctypes.c_void_p * (nslices - 1))(*[b.data_ptr() for b in bqs])
+    Xd = X.to(dev)
+    outs = []
+    for rep in range(2):
+        Gd = G0.to(dev)
+        R = torch.zeros((1 + nslices, ops.AMAX_RECORD_FLOATS), device=dev)      # [0] the incoming bound, [1 + c] slice c
+        R[0, 0] = Gd[..., grp].abs().max()
+        R[nslices, 32] = Gd[..., C0 + (nslices - 1) * F:C0 + nslices * F].abs().max()   # the last slice: final before the chain
+        _lib.prof_reset()
+        _lib.prof_enable(True)
+        _lib.check(L.otgan_dense16_chain_bwd_f32(N, H, H, nslices, Gd.data_ptr() + 4 * C0, Ctot, Xd.data_ptr() + 4 * C0, Ctot,
+                                                 ctypes.cast(pb, ctypes.c_void_p), R[0].data_ptr(), R[1].data_ptr(),
+                                                 _lib.stream_ptr()), "chain_bwd")
+        torch.cuda.synchronize()
+        launches = _lib.prof_collect()["conv_dgrad"]["launches"]
+        _lib.prof_enable(False)
+        assert launches == (1 if H == 8 else nslices - 1), launches
+        outs.append((Gd.cpu(), R.cpu()))
+    assert torch.equal(outs[0][0], outs[1][0]) and torch.equal(outs[0][1], outs[1][1])
+    got, R = outs[0]
+    last = C0 + (nslices - 1) * F
+    assert torch.equal(got[..., :C0], G0[..., :C0]) and torch.equal(got[..., last:], G0[..., last:])
+    worst = 0.0
+    for c in range(nslices - 1):
+        a, b = got[..., C0 + 16 * c:C0 + 16 * c + 16].double(), want[..., 16 * c:16 * c + 16]
+        err = float((a - b).norm() / b.norm())
+        worst = max(worst, err)
+        print(f"chain backward H={H} N={N} nslices={nslices} slice {c}: rel L2 {err:.3e}")
+        assert err < 2e-5, (c, err)
+        assert float(R[1 + c].max()) == float(got[..., C0 + 16 * c:C0 + 16 * c + 16].abs().max()), c
+    print(f"chain backward H={H} N={N} nslices={nslices}: worst slice {worst:.3e}")
 
 
 _BLOCK_WORKER = r"""

@@ -12,6 +12,7 @@ import pytest
 import torch
 
 from oracle import nets_torch as NT
+from tests import dense16_ref as D16
 from tests import densenet64_ref as R64
 
 pytestmark = pytest.mark.gpu
@@ -39,15 +40,6 @@ def _oracle_params(template):
         layer, leaf = name.rsplit("/", 1)
         P.setdefault(layer, {})[leaf] = v.detach().double().cpu().requires_grad_(True)
     return P
-
-
-def _crelu_slices(xs):
-    """[N,H,W,16 n] -> [N, 32 n, H, W]: the slices interleaved [x_0, -x_0, x_1, -x_1, ...] and rectified (utils/nn.py:198-200)."""
-    parts = []
-    for s in range(xs.shape[-1] // 16):
-        sl = xs[..., 16 * s:16 * s + 16]
-        parts += [sl.clamp(min=0), (-sl).clamp(min=0)]
-    return torch.cat(parts, -1).permute(0, 3, 1, 2)
 
 
 # ------------------------------------------------------------------------------- 1: growth forward at W = 64
@@ -84,7 +76,7 @@ def test_growth_forward_64_vs_fp64(dev, N, H, n_own):
     ops.conv_fwd_raw(desc, buf[..., C0 + g0 * F:], cmap, wT, None, buf, fq)
     got = buf[..., C0 + k * F:C0 + (k + 1) * F].double().cpu()
     w = wT.double().cpu().reshape(16, 9, 32 * n_own).permute(0, 2, 1).reshape(16, 32 * n_own, 3, 3)
-    want = y0 + torch.nn.functional.conv2d(_crelu_slices(xs), w, padding=1).permute(0, 2, 3, 1)
+    want = y0 + torch.nn.functional.conv2d(D16.crelu_slices(xs), w, padding=1).permute(0, 2, 3, 1)
     err = float((got - want).norm() / want.norm())
     print(f"growth forward N={N} n_own={n_own}: rel L2 {err:.3e}")
     assert err < TOL, err
@@ -106,60 +98,7 @@ def test_growth_backward_by_slice_64_vs_fp64(dev, N, npairs):
     `npairs` later layers of the group, layer k = 1 .. npairs reading slices [0, k) (CReLU backward, reference
     utils/nn.py:198-200).  Reference: fp64 autograd of sum_k <G_k, conv3x3(crelu(slices [0, k)), w_k)> with respect to slice 0,
     added onto the gradient the slice already holds."""
-    from otgan_amd import _lib, ops
-    from otgan_amd._lib_layers import Dense16BwdPair
-    L = _lib.lib()
-    H, F = 64, 16
-    g = torch.Generator().manual_seed(100 + N + npairs)
-    S = npairs + 1                                                        # slices of the group
-    ld = S * F + 16                                                       # (a row stride wider than the group)
-    X = torch.randn(N, H, H, ld, generator=g)
-    G = torch.randn(N, H, H, ld, generator=g)
-    G[..., 2 * F:3 * F] *= 37.0                                           # source slices of different magnitudes
-    G[3 % N] *= 5.0
-    # layer k: HWIO weights [9][32 k][16] and their transpose wT [16][9 * 32 k] (what the forward prepare call takes)
-    ws = [(torch.randn(9, 2 * F * k, F, generator=g) * 0.05) for k in range(1, S)]
-    wTs = [w.reshape(9 * 2 * F * (k + 1), F).t().contiguous() for k, w in enumerate(ws)]
-    # fp64 reference
-    x0 = X[..., :F].double().requires_grad_(True)
-    total = 0.0
-    for k in range(1, S):
-        xs = torch.cat([x0, X[..., F:k * F].double()], -1)
-        w = ws[k - 1].double().reshape(3, 3, 2 * F * k, F).permute(3, 2, 0, 1)
-        y = torch.nn.functional.conv2d(_crelu_slices(xs), w, padding=1).permute(0, 2, 3, 1)
-        total = total + (y * G[..., k * F:(k + 1) * F].double()).sum()
-    want = G[..., :F].double() + torch.autograd.grad(total, x0)[0]
-
-    Xd, Gd = X.to(dev), G.to(dev)
-    wd, wTd = [w.to(dev) for w in ws], [w.to(dev) for w in wTs]
-    nsl = list(range(1, S))
-    fwd = [torch.empty(int(L.otgan_dense16_filter_bytes(n)), dtype=torch.uint8, device=dev) for n in nsl]
-    n = len(nsl)
-    pw = (ctypes.c_void_p * n)(*[w.data_ptr() for w in wTd])
-    pn = (ctypes.c_int * n)(*nsl)
-    pf = (ctypes.c_void_p * n)(*[f.data_ptr() for f in fwd])
-    _lib.check(L.otgan_dense16_prepare_filters_f32(ctypes.cast(pw, ctypes.c_void_p), ctypes.cast(pn, ctypes.c_void_p),
-                                                   ctypes.cast(pf, ctypes.c_void_p), n, _lib.stream_ptr()), "prepare")
-    bq = torch.empty(int(L.otgan_dense16_bwd_filter_bytes(npairs)), dtype=torch.uint8, device=dev)
-    pairs = [Dense16BwdPair(wd[j].data_ptr(), fwd[j].data_ptr(), bq.data_ptr(), 1 + j, 0, j) for j in range(npairs)]
-    arr = (Dense16BwdPair * npairs)(*pairs)
-    _lib.check(L.otgan_dense16_prepare_bwd_filters_f32(ctypes.cast(arr, ctypes.c_void_p), npairs, ctypes.cast(pf, ctypes.c_void_p),
-                                                       n, _lib.stream_ptr()), "prepare_bwd")
-    # records: one bounding record, then one per source slice (as otgan_dense16_chain_bwd_f32 passes them), then the output's
-    R = torch.zeros((2 + npairs, ops.AMAX_RECORD_FLOATS), device=dev)
-    for j in range(npairs):
-        R[1 + j, 32 * (j % 16)] = Gd[..., (1 + j) * F:(2 + j) * F].abs().max()
-    before = Gd.clone()
-    _lib.check(L.otgan_dense16_bwd_slice_f32(N, H, H, npairs, Gd.data_ptr() + 4 * F, ld, bq.data_ptr(), Xd.data_ptr(), ld,
-                                             Gd.data_ptr(), R[0].data_ptr(), 1, R[1].data_ptr(), npairs,
-                                             R[1 + npairs].data_ptr(), _lib.stream_ptr()), "bwd_slice")
-    torch.cuda.synchronize()
-    got = Gd[..., :F].double().cpu()
-    err = float((got - want).norm() / want.norm())
-    print(f"growth backward N={N} npairs={npairs}: rel L2 {err:.3e}")
-    assert err < TOL, err
-    assert torch.equal(Gd[..., F:], before[..., F:])                     # only slice 0 is written
-    assert float(R[1 + npairs].max()) == float(got.abs().max().float())
+    D16.growth_backward_by_slice(dev, N, 64, npairs, TOL)
 
 
 # ------------------------------------------------------------------------------- 3: a whole dense block at 64 x 64
