@@ -462,6 +462,25 @@ int otgan_incep_head_f32(int N, int HW, int C, int ldx, int classes, const float
 int otgan_moments_update_f64(int n, int C, int ldx, const float* x, double* sum, double* outer, void* stream);
 
 /*
+ * Kernel sums of the Kernel Inception Distance (utils/kid.py), fp64 MFMA, all subsets in one call.  For subset s with
+ * X_i = x[xi[s][i]], Y_j = y[yi[s][j]] (i, j < m) and k(a, b) = (a . b / C + 1)^3:
+ *   out[s][0] = sum_{i != j} k(X_i, X_j),   out[s][1] = sum_{i != j} k(Y_i, Y_j),   out[s][2] = sum_{i, j} k(X_i, Y_j).
+ * x, y: fp32 rows of C channels with row strides ldx, ldy >= C (pool3 of otgan_incep_head_f32, or a column slice of a wider
+ * buffer), 16-byte aligned with strides that are multiples of 4; xi, yi: int32 [nsub][m] row numbers into x and y -- NOT
+ * validated here, the caller makes them and checks them; out: double [nsub][3], OVERWRITTEN.  i != j is by position in the
+ * list: a row number that occurs twice counts as two rows.  Any m >= 2, any C % 4 == 0, nsub <= 65535 (nsub == 0 launches
+ * nothing).  The fp32 inputs are converted to fp64 before the multiply, so every product is exact; the affine map, the cube
+ * and all sums are fp64.  No Gram matrix is written: 64 x 64 blocks (only those on or above the diagonal of the two symmetric
+ * Grams) are reduced in registers to one double each in `workspace` (otgan_kid_workspace_bytes(nsub, m) bytes, 8-byte
+ * aligned) and a second launch adds them per subset in a fixed order.  Deterministic (no atomics): the same call gives the
+ * same bits, and a subset's value does not depend on the other subsets of the call.  An argument error returns nonzero
+ * without touching out.
+ */
+size_t otgan_kid_workspace_bytes(int nsub, int m);
+int otgan_kid_sums_f64(int nsub, int m, int C, const float* x, int ldx, const int32_t* xi, const float* y, int ldy,
+                       const int32_t* yi, double* out, void* workspace, size_t workspace_bytes, void* stream);
+
+/*
  * The training batch from a device-resident uint8 dataset in ONE launch (csrc/data.hip; utils/data.py): gather by the
  * epoch's permutation, per-image horizontal flip, uint8 -> [-1, 1] and an optional integer box-downsample -- what the
  * reference does on the host per step (train.py:158,163-170,209-211).

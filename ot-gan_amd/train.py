@@ -14,6 +14,7 @@ reference is 32 x 32 only), --save_every,
 --data_dependent_init, --eval_every / --eval_samples / --inception_model (the reference's Inception-score hook,
 train.py:245-272: --inception_model takes the reference's own 2015 graph file, or a TorchScript classifier),
 --fid_stats / --fid_real_samples (the Frechet Inception Distance beside every score, utils/fid.py),
+--kid_subsets / --kid_subset_size / --kid_real_samples (the Kernel Inception Distance beside them, utils/kid.py),
 --dataset cifar10|imagenet64|npy and --data_on_device (utils/data.py): the training set lives on the device as uint8 and
 one kernel launch per step gathers, flips and converts the step's batch; 64 x 64 data (the downsampled-ImageNet pickles, a
 .npy of one's own images) comes in this way only.  Guarantee: `--dataset cifar10 --data_on_device` feeds `model.step` the
@@ -82,6 +83,14 @@ def build_parser():
                         "--inception_model.  '' = off")
     p.add_argument('--fid_real_samples', type=int, default=0,
                    help='training images behind a computed --fid_stats file: the first N (0 = all)')
+    p.add_argument('--kid_subsets', type=int, default=0,
+                   help='report the Kernel Inception Distance (utils/kid.py: unbiased, so comparable across --eval_samples) beside '
+                        'every Inception score as the mean and std of the MMD^2 of this many random subsets of the generated and '
+                        'the real pool_3 features (papers use 100).  Needs the 2015 graph as --inception_model.  0 = off')
+    p.add_argument('--kid_subset_size', type=int, default=1000,
+                   help='rows per KID subset and side; cut to the rows the smallest rank holds')
+    p.add_argument('--kid_real_samples', type=int, default=0,
+                   help='training images behind the real side of KID: the first N (0 = min(eval_samples, training images))')
     p.add_argument('--step_graph', type=int, nargs='?', const=1, default=None, choices=(0, 1),
                    help='replay whole steps as hipGraphs after the first period (single-process runs; bit-identical to the '
                         'eager steps).  Default: on for --model densenet (launch-bound: replay 25.5 ms against 27.6 - 29.6 ms), '
@@ -111,7 +120,12 @@ def inception_hook(model, args, classifier, state, rank=0, world=1):
     With the real data's pool_3 statistics in `state["fid_real"]` = (mu, sigma) (--fid_stats; device classifier only) the
     same forward pass also feeds the Frechet Inception Distance (utils/fid.py): pool_3 of exactly the `eval_samples`
     samples the score covers goes into fp64 moments on the device, one SUM all-reduce per evaluated model replaces a
-    feature gather, rank 0 finalises on the host and broadcasts the scalar."""
+    feature gather, rank 0 finalises on the host and broadcasts the scalar.
+
+    With --kid_subsets > 0 and the real data's features in `state["kid_real"]` (a utils.kid.FeatureBank; device classifier
+    only) the same pool_3 rows -- this rank's `mine` rows that survive the cut to `eval_samples` -- also fill a feature
+    bank on the device, and the Kernel Inception Distance (utils/kid.py) of every evaluated model is reported as
+    (mean, std) over the subsets: one fused kernel-sum launch per rank, one small all-reduce."""
     from .utils.inception import class_probabilities, inception_score_from_probs
     from . import parallel
     on_device = hasattr(classifier, "probs_from_generator")    # utils.inception_net.InceptionNet: samples stay on the GPU
@@ -119,21 +133,36 @@ def inception_hook(model, args, classifier, state, rank=0, world=1):
     share = -(-args.eval_samples // world)
     # the gather below is cut to eval_samples rows: of this rank's share the first `mine` survive
     mine = min(max(args.eval_samples - rank * share, 0), share)
+    kid_real = state.get("kid_real") if on_device and getattr(args, "kid_subsets", 0) > 0 else None
     out = {}
     if fid_real is not None:
         from .utils import fid
         state.setdefault("fid_min", float("inf"))
         state.setdefault("fid_iter", 0)
+    if kid_real is not None:
+        from .utils import kid
+        state.setdefault("kid_min", float("inf"))
+        state.setdefault("kid_iter", 0)
+        if "kid_m" not in state:
+            state["kid_m"] = kid.effective_subset_size(args.kid_subset_size, args.eval_samples, kid_real.total, world)
+        if "kid_gen" not in state or state["kid_gen"].buf.shape[0] < mine:      # one buffer for every evaluation of the run
+            state["kid_gen"] = kid.FeatureBank(mine, classifier.plan.pool3_channels, classifier.device, total=args.eval_samples)
     for tag, ema in (("", False), ("EMA ", True)):
         probs, have = [], 0
         if fid_real is not None:
             acc = fid.MomentAccumulator(classifier.plan.pool3_channels, classifier.device)
+        if kid_real is not None:
+            state["kid_gen"].clear()
         while have < share:
             x = model.sample(min(1000, share - have), ema=ema)
-            if fid_real is not None:
+            if fid_real is not None or kid_real is not None:
                 p, pool3 = classifier.probs_and_pool3_from_generator(x.float())
                 probs.append(p)
-                acc.update(pool3[:min(max(mine - have, 0), x.shape[0])])
+                kept = pool3[:min(max(mine - have, 0), x.shape[0])]
+                if fid_real is not None:
+                    acc.update(kept)
+                if kid_real is not None:
+                    state["kid_gen"].append(kept)
             elif on_device:
                 probs.append(classifier.probs_from_generator(x.float()))                      # 127.5 (x + 1) folded in
             else:
@@ -161,10 +190,19 @@ def inception_hook(model, args, classifier, state, rank=0, world=1):
             if d < state.get("fid_min", float("inf")):
                 state["fid_min"], state["fid_iter"] = d, state["epoch"]
             out["fid_" + (tag.strip() or "live")] = d
+        if kid_real is not None:
+            k = kid.kid(state["kid_gen"], kid_real, args.kid_subsets, state["kid_m"], getattr(args, "seed", 1), rank, world)
+            if rank == 0:
+                print('%sKID was %.6f, std was %.6f' % (tag, k[0], k[1]))
+            if k[0] < state["kid_min"]:
+                state["kid_min"], state["kid_iter"] = k[0], state["epoch"]
+            out["kid_" + (tag.strip() or "live")] = k
     if rank == 0:
         print('max inception score was %.6f, iter was %d' % (state["max"], state["iter"]))
         if fid_real is not None:
             print('min FID was %.4f, iter was %d' % (state["fid_min"], state["fid_iter"]))
+        if kid_real is not None:
+            print('min KID was %.6f, iter was %d' % (state["kid_min"], state["kid_iter"]))
     return out
 
 
@@ -194,6 +232,29 @@ def real_fid_stats(args, classifier, trainx, rank=0, world=1):
         fid.save_stats(args.fid_stats, mu, sigma, n)
         print('FID statistics of the real data: computed from %d training images, saved to %s' % (n, args.fid_stats))
     return mu, sigma
+
+
+def real_kid_state(args, classifier, trainx, rank=0, world=1):
+    """--kid_subsets: what the hook keeps in its state for the Kernel Inception Distance -- {"kid_real": the pool_3 of the
+    first --kid_real_samples training images as a device feature bank (this rank's share), "kid_m": the subset size in
+    effect}.  Empty (said once) when the classifier is not the device network of the 2015 graph.  A subset size below 2
+    is a ValueError before anything is classified."""
+    from .utils import kid
+    if not hasattr(classifier, "probs_and_pool3_from_generator"):
+        if rank == 0:
+            print('--kid_subsets: KID needs the 2015 Inception graph as --inception_model (it is defined on its pool_3); skipped')
+        return {}
+    n = min(args.kid_real_samples or args.eval_samples, trainx.shape[0])
+    m = kid.effective_subset_size(args.kid_subset_size, args.eval_samples, n, world)
+    if rank == 0 and m < args.kid_subset_size:
+        print('KID subsets hold %d rows, not --kid_subset_size %d: the smallest rank has no more generated or real rows'
+              % (m, args.kid_subset_size))
+    x = trainx.head(n) if hasattr(trainx, "head") else trainx[:n]      # (a utils.data.DeviceDataset has no slices)
+    bank = kid.real_bank(classifier, x, n, rank, world)
+    if rank == 0:
+        print('KID features of the real data: pool_3 of the first %d training images, kept on the device (%.1f MB per rank)'
+              % (n, bank.buf.numel() * 4 / 1e6))
+    return {"kid_real": bank, "kid_m": m}
 
 
 def load_cifar(data_dir, subset='train'):
@@ -310,6 +371,8 @@ def main(argv=None, self_launch=False):
         print('no --inception_model: the Inception-score hook (reference train.py:245-272) is skipped')
     if args.fid_stats:
         score_state["fid_real"] = real_fid_stats(args, classifier, trainx, rank, world)
+    if args.kid_subsets > 0:
+        score_state.update(real_kid_state(args, classifier, trainx, rank, world))
     start_time = time.time()
     total = 0
     for epoch in range(current_epoch, 1000000):

@@ -1,6 +1,6 @@
 """Throughput of the Inception evaluation network (utils/inception_net.py, csrc/inception.hip) on one GPU.
 
-    python tools/bench_inception.py [--graph classify_image_graph_def.pb | .tgz | dir] [--batch 500] [--moments]
+    python tools/bench_inception.py [--graph classify_image_graph_def.pb | .tgz | dir] [--batch 500] [--moments] [--kid]
 
 Without --graph it synthesizes the full 2015 topology with random weights (tests/inception_graphs.py: same layers,
 same FLOP count).  Input: generator-like 32 x 32 images in [-1, 1] through probs_from_generator (the training hook's
@@ -8,7 +8,11 @@ path: resize to 299 x 299 and the affines in one kernel).  Prints img/s and TFLO
 FLOP count and HIP-event timing after warm-up, and the projected time of one evaluation of the reference
 (2 x 50 000 samples, train.py:245-272), as one JSON line.  --moments: also the time of one fp64 moment update of the
 batch's pool_3 (utils/fid.py, csrc/moments.hip; HIP events, same run) beside the forward pass, and the wall time of the
-host finalisation of one Frechet distance at that width (two eigh).
+host finalisation of one Frechet distance at that width (two eigh).  --kid: also the time of ONE `kid_sums` call of the
+Kernel Inception Distance (utils/kid.py, csrc/kid.hip; HIP events, same run) at its usual setting -- 100 subsets of 1000
+rows -- on two banks of max(batch, 1000) rows at the graph's pool_3 width (the network's pool_3 of random images when the
+batch has 1000, pool_3-like synthetic rows otherwise), its fp64 rate counting 2 m^2 C 2 per subset, and its share of the
+forward passes of the 50 000 samples it follows.
 """
 import argparse
 import json
@@ -29,6 +33,7 @@ def main():
     ap.add_argument("--iters", type=int, default=5)
     ap.add_argument("--image_size", type=int, default=32)
     ap.add_argument("--moments", action="store_true", help="time the FID moment update of the batch's pool_3 as well")
+    ap.add_argument("--kid", action="store_true", help="time one KID kernel-sum call (100 subsets x 1000 rows) as well")
     a = ap.parse_args()
     import torch
     from otgan_amd.utils import inception_net, tfgraph
@@ -82,6 +87,31 @@ def main():
                     "moments_fp64_tflops": round(2.0 * a.batch * C * C / (mms * 1e-3) / 1e12, 2), "pool3_channels": C,
                     "allreduce_mb": round(8 * (C * C + C + 1) / 1e6, 1), "feature_gather_mb_50000": round(4 * 50000 * C / 1e6, 1),
                     "fid_finalise_s": round(time.time() - t0, 2), "fid_finite": bool(d == d and abs(d) != float("inf"))})
+    if a.kid:
+        from otgan_amd.utils import kid
+        C, nsub, m = plan.pool3_channels, 100, 1000
+        rows = max(a.batch, m)
+        if a.batch >= m:
+            banks = [net.run(x, 127.5, 127.5)[0], net.run(x.flip(0).neg(), 127.5, 127.5)[0]]
+        else:       # non-negative, a scale per channel: the statistics of pool_3, not its values
+            banks = [torch.rand((rows, C), generator=g, device=dev) * torch.rand((1, C), generator=g, device=dev) for _ in range(2)]
+        xi, yi = kid.subset_indices(rows, m, nsub, 0, 0), kid.subset_indices(rows, m, nsub, 0, 1)
+        xi, yi = torch.as_tensor(xi, device=dev), torch.as_tensor(yi, device=dev)
+        for _ in range(a.warmup):
+            sums = kid.kid_sums(banks[0], xi, banks[1], yi)
+        torch.cuda.synchronize()
+        e0.record()
+        for _ in range(a.iters):
+            sums = kid.kid_sums(banks[0], xi, banks[1], yi)
+        e1.record()
+        torch.cuda.synchronize()
+        kms = e0.elapsed_time(e1) / a.iters
+        v = kid.mmd2_from_sums(sums, m).cpu().numpy()
+        forward_ms_50000 = ms * (50000 / a.batch)
+        out.update({"kid_ms": round(kms, 3), "kid_fp64_tflops": round(nsub * 2.0 * m * m * C * 2 / (kms * 1e-3) / 1e12, 2),
+                    "kid_share_of_eval": round(kms / forward_ms_50000, 5), "kid_subsets": nsub, "kid_subset_size": m,
+                    "kid_bank_rows": rows, "kid_features": "pool_3 of the graph" if a.batch >= m else "synthetic",
+                    "pool3_channels": C, "kid_mean": float(v.mean()), "kid_std": float(v.std())})
     print(json.dumps(out))
 
 
