@@ -481,6 +481,31 @@ int otgan_kid_sums_f64(int nsub, int m, int C, const float* x, int ldx, const in
                        const int32_t* yi, double* out, void* workspace, size_t workspace_bytes, void* stream);
 
 /*
+ * Nearest-neighbour passes of precision / recall / density / coverage (utils/pr.py; the improved precision and recall of
+ * the guided-diffusion evaluator, evaluations/evaluator.py ManifoldEstimator, and prdc's compute_prdc), fp64 MFMA, the
+ * distance matrix never written.  With d2(a, b) = max(0, (a.a + b.b) - 2 a.b), for every query row i < nq over the
+ * columns j < ny with j != self0 + i (self0 = -1: no column is excluded):
+ *   nearest[i][0 .. k) = the k smallest d2(q_i, y_j), ascending; +inf where fewer than k columns were counted,
+ *   inside[i]          = #{ j : d2(q_i, y_j) <= thresh[j] }.
+ * q, y: fp32 rows of C channels with row strides ldq, ldy >= C, 16-byte aligned with strides that are multiples of 4 (the
+ * rules of otgan_kid_sums_f64); thresh: double [ny]; nearest: double [nq][k]; inside: int32 [nq]; both OVERWRITTEN.
+ * 0 <= k <= 8, nearest may be null with k == 0; thresh and inside are both null or both given (with ny == 0 there is no
+ * threshold to point at and thresh may be null beside an inside, which becomes 0).  The exclusion is by
+ * POSITION: another row with the same values is a neighbour at distance 0.  The fp32 inputs are converted to fp64 before
+ * the multiply, every dot product -- the norms among them -- adds its channels in an order that depends on C only, so
+ * d2(a, b) and d2(b, a) are the same bits in any call, tile or operand role and d2(a, a) == 0.  A k-smallest list and a
+ * count are order-free, so the outputs do not depend on the order of the columns, on a row's place in the call or on how
+ * the columns are split over workgroups; no atomics.  workspace: otgan_knn_workspace_bytes(nq, ny, k) bytes, 8-byte
+ * aligned -- the norms of q and y and k doubles + one count per (column split, query row); OTGAN_ERR_WORKSPACE when
+ * smaller.  nq == 0 or ny == 0 returns OTGAN_OK (ny == 0: nearest = +inf, inside = 0).  An argument error returns
+ * nonzero without touching the outputs.
+ */
+size_t otgan_knn_workspace_bytes(int nq, int ny, int k);
+int otgan_knn_f64(int nq, int ny, int C, const float* q, int ldq, const float* y, int ldy, int k, int self0,
+                  const double* thresh, double* nearest, int32_t* inside, void* workspace, size_t workspace_bytes,
+                  void* stream);
+
+/*
  * The training batch from a device-resident uint8 dataset in ONE launch (csrc/data.hip; utils/data.py): gather by the
  * epoch's permutation, per-image horizontal flip, uint8 -> [-1, 1] and an optional integer box-downsample -- what the
  * reference does on the host per step (train.py:158,163-170,209-211).

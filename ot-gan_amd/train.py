@@ -15,6 +15,7 @@ reference is 32 x 32 only), --save_every,
 train.py:245-272: --inception_model takes the reference's own 2015 graph file, or a TorchScript classifier),
 --fid_stats / --fid_real_samples (the Frechet Inception Distance beside every score, utils/fid.py),
 --kid_subsets / --kid_subset_size / --kid_real_samples (the Kernel Inception Distance beside them, utils/kid.py),
+--pr_neighbours / --pr_real_samples (precision, recall, density and coverage beside them, utils/pr.py),
 --dataset cifar10|imagenet64|npy and --data_on_device (utils/data.py): the training set lives on the device as uint8 and
 one kernel launch per step gathers, flips and converts the step's batch; 64 x 64 data (the downsampled-ImageNet pickles, a
 .npy of one's own images) comes in this way only.  Guarantee: `--dataset cifar10 --data_on_device` feeds `model.step` the
@@ -91,6 +92,14 @@ def build_parser():
                    help='rows per KID subset and side; cut to the rows the smallest rank holds')
     p.add_argument('--kid_real_samples', type=int, default=0,
                    help='training images behind the real side of KID: the first N (0 = min(eval_samples, training images))')
+    p.add_argument('--pr_neighbours', type=int, default=0,
+                   help='report precision and recall (Kynkaanniemi et al. 2019) and density and coverage (Naeem et al. 2020) of '
+                        'the generated against the real pool_3 features beside every Inception score (utils/pr.py), with balls '
+                        'reaching to the K-th nearest neighbour (the papers use 3; at most 8).  Needs the 2015 graph as '
+                        '--inception_model.  0 = off')
+    p.add_argument('--pr_real_samples', type=int, default=0,
+                   help='training images behind the real side of precision and recall: the first N (0 = min(eval_samples, '
+                        'training images))')
     p.add_argument('--step_graph', type=int, nargs='?', const=1, default=None, choices=(0, 1),
                    help='replay whole steps as hipGraphs after the first period (single-process runs; bit-identical to the '
                         'eager steps).  Default: on for --model densenet (launch-bound: replay 25.5 ms against 27.6 - 29.6 ms), '
@@ -125,7 +134,11 @@ def inception_hook(model, args, classifier, state, rank=0, world=1):
     With --kid_subsets > 0 and the real data's features in `state["kid_real"]` (a utils.kid.FeatureBank; device classifier
     only) the same pool_3 rows -- this rank's `mine` rows that survive the cut to `eval_samples` -- also fill a feature
     bank on the device, and the Kernel Inception Distance (utils/kid.py) of every evaluated model is reported as
-    (mean, std) over the subsets: one fused kernel-sum launch per rank, one small all-reduce."""
+    (mean, std) over the subsets: one fused kernel-sum launch per rank, one small all-reduce.
+
+    With --pr_neighbours K > 0 and `state["pr_real"]` / `state["pr_real_radii"]` (real_pr_state; device classifier only) the
+    same bank -- filled when either KID or this is on -- also gives (precision, recall, density, coverage) of every
+    evaluated model (utils/pr.py): three fused k-NN passes, the same values for every world size."""
     from .utils.inception import class_probabilities, inception_score_from_probs
     from . import parallel
     on_device = hasattr(classifier, "probs_from_generator")    # utils.inception_net.InceptionNet: samples stay on the GPU
@@ -134,6 +147,8 @@ def inception_hook(model, args, classifier, state, rank=0, world=1):
     # the gather below is cut to eval_samples rows: of this rank's share the first `mine` survive
     mine = min(max(args.eval_samples - rank * share, 0), share)
     kid_real = state.get("kid_real") if on_device and getattr(args, "kid_subsets", 0) > 0 else None
+    pr_k = getattr(args, "pr_neighbours", 0)
+    pr_real = state.get("pr_real") if on_device and pr_k > 0 else None
     out = {}
     if fid_real is not None:
         from .utils import fid
@@ -145,23 +160,26 @@ def inception_hook(model, args, classifier, state, rank=0, world=1):
         state.setdefault("kid_iter", 0)
         if "kid_m" not in state:
             state["kid_m"] = kid.effective_subset_size(args.kid_subset_size, args.eval_samples, kid_real.total, world)
+    if pr_real is not None:
+        from .utils import kid, pr
+    if kid_real is not None or pr_real is not None:
         if "kid_gen" not in state or state["kid_gen"].buf.shape[0] < mine:      # one buffer for every evaluation of the run
             state["kid_gen"] = kid.FeatureBank(mine, classifier.plan.pool3_channels, classifier.device, total=args.eval_samples)
     for tag, ema in (("", False), ("EMA ", True)):
         probs, have = [], 0
         if fid_real is not None:
             acc = fid.MomentAccumulator(classifier.plan.pool3_channels, classifier.device)
-        if kid_real is not None:
+        if kid_real is not None or pr_real is not None:
             state["kid_gen"].clear()
         while have < share:
             x = model.sample(min(1000, share - have), ema=ema)
-            if fid_real is not None or kid_real is not None:
+            if fid_real is not None or kid_real is not None or pr_real is not None:
                 p, pool3 = classifier.probs_and_pool3_from_generator(x.float())
                 probs.append(p)
                 kept = pool3[:min(max(mine - have, 0), x.shape[0])]
                 if fid_real is not None:
                     acc.update(kept)
-                if kid_real is not None:
+                if kid_real is not None or pr_real is not None:
                     state["kid_gen"].append(kept)
             elif on_device:
                 probs.append(classifier.probs_from_generator(x.float()))                      # 127.5 (x + 1) folded in
@@ -197,6 +215,11 @@ def inception_hook(model, args, classifier, state, rank=0, world=1):
             if k[0] < state["kid_min"]:
                 state["kid_min"], state["kid_iter"] = k[0], state["epoch"]
             out["kid_" + (tag.strip() or "live")] = k
+        if pr_real is not None:
+            v = pr.precision_recall(state["kid_gen"], pr_real, pr_k, state["pr_real_radii"], rank, world)
+            if rank == 0:
+                print('%sprecision was %.4f, recall was %.4f, density was %.4f, coverage was %.4f' % ((tag,) + v))
+            out["pr_" + (tag.strip() or "live")] = v
     if rank == 0:
         print('max inception score was %.6f, iter was %d' % (state["max"], state["iter"]))
         if fid_real is not None:
@@ -255,6 +278,32 @@ def real_kid_state(args, classifier, trainx, rank=0, world=1):
         print('KID features of the real data: pool_3 of the first %d training images, kept on the device (%.1f MB per rank)'
               % (n, bank.buf.numel() * 4 / 1e6))
     return {"kid_real": bank, "kid_m": m}
+
+
+def real_pr_state(args, classifier, trainx, rank=0, world=1, kid_bank=None):
+    """--pr_neighbours: what the hook keeps in its state for precision, recall, density and coverage -- {"pr_real": the
+    pool_3 of the first --pr_real_samples training images as a device feature bank (this rank's share; `kid_bank`, the
+    bank KID keeps, when that holds the same images), "pr_real_radii": the K-th neighbour radius of every real row over
+    all ranks, computed once}.  Empty (said once) when the classifier is not the device network of the 2015 graph.  A
+    side with no more than K rows is a ValueError before anything is classified."""
+    from .utils import kid, pr
+    if not hasattr(classifier, "probs_and_pool3_from_generator"):
+        if rank == 0:
+            print('--pr_neighbours: precision and recall need the 2015 Inception graph as --inception_model (they are defined '
+                  'on its pool_3); skipped')
+        return {}
+    n = min(args.pr_real_samples or args.eval_samples, trainx.shape[0])
+    k = pr.check_neighbours(args.pr_neighbours, args.eval_samples, n)
+    shared = kid_bank is not None and kid_bank.total == n
+    if shared:
+        bank = kid_bank
+    else:
+        x = trainx.head(n) if hasattr(trainx, "head") else trainx[:n]      # (a utils.data.DeviceDataset has no slices)
+        bank = kid.real_bank(classifier, x, n, rank, world)
+    if rank == 0:
+        print('precision / recall features of the real data: pool_3 of the first %d training images, %s (%.1f MB per rank)'
+              % (n, 'the bank KID keeps' if shared else 'kept on the device', bank.buf.numel() * 4 / 1e6))
+    return {"pr_real": bank, "pr_real_radii": pr.radii(bank.rows, k, rank, world)}
 
 
 def load_cifar(data_dir, subset='train'):
@@ -373,6 +422,8 @@ def main(argv=None, self_launch=False):
         score_state["fid_real"] = real_fid_stats(args, classifier, trainx, rank, world)
     if args.kid_subsets > 0:
         score_state.update(real_kid_state(args, classifier, trainx, rank, world))
+    if args.pr_neighbours > 0:
+        score_state.update(real_pr_state(args, classifier, trainx, rank, world, score_state.get("kid_real")))
     start_time = time.time()
     total = 0
     for epoch in range(current_epoch, 1000000):

@@ -800,7 +800,8 @@ def default_args(**over):
              image_size=32, matching_scope='global', synthetic=False, max_steps=0, save_every=200,
              synthetic_size=50000, data_dependent_init=False, eval_every=100, eval_samples=50000,
              inception_model='', ranks=0, step_graph=None, fid_stats='', fid_real_samples=0, dataset='cifar10',
-             data_on_device=False, kid_subsets=0, kid_subset_size=1000, kid_real_samples=0)
+             data_on_device=False, kid_subsets=0, kid_subset_size=1000, kid_real_samples=0,
+             pr_neighbours=0, pr_real_samples=0)
     d.update(over)
     return argparse.Namespace(**d)
 

@@ -1,6 +1,6 @@
 """Throughput of the Inception evaluation network (utils/inception_net.py, csrc/inception.hip) on one GPU.
 
-    python tools/bench_inception.py [--graph classify_image_graph_def.pb | .tgz | dir] [--batch 500] [--moments] [--kid]
+    python tools/bench_inception.py [--graph classify_image_graph_def.pb | .tgz | dir] [--batch 500] [--moments] [--kid] [--pr]
 
 Without --graph it synthesizes the full 2015 topology with random weights (tests/inception_graphs.py: same layers,
 same FLOP count).  Input: generator-like 32 x 32 images in [-1, 1] through probs_from_generator (the training hook's
@@ -12,7 +12,11 @@ host finalisation of one Frechet distance at that width (two eigh).  --kid: also
 Kernel Inception Distance (utils/kid.py, csrc/kid.hip; HIP events, same run) at its usual setting -- 100 subsets of 1000
 rows -- on two banks of max(batch, 1000) rows at the graph's pool_3 width (the network's pool_3 of random images when the
 batch has 1000, pool_3-like synthetic rows otherwise), its fp64 rate counting 2 m^2 C 2 per subset, and its share of the
-forward passes of the 50 000 samples it follows.
+forward passes of the 50 000 samples it follows.  --pr: also the time of the four k-NN passes behind precision, recall,
+density and coverage of one model (utils/pr.py, csrc/knn.hip; HIP events, same run) at --pr_rows generated and as many
+real rows, K = 3 -- the radii of the real rows, those of the generated rows, generated against real, real against
+generated -- its fp64 rate counting 2 nq ny C per pass, and its share of the same forward passes.  The yardstick of that
+rate is kid_fp64_tflops of the same run (--kid): the same block product with a cheaper epilogue.
 """
 import argparse
 import json
@@ -34,6 +38,8 @@ def main():
     ap.add_argument("--image_size", type=int, default=32)
     ap.add_argument("--moments", action="store_true", help="time the FID moment update of the batch's pool_3 as well")
     ap.add_argument("--kid", action="store_true", help="time one KID kernel-sum call (100 subsets x 1000 rows) as well")
+    ap.add_argument("--pr", action="store_true", help="time the four k-NN passes of precision / recall / density / coverage as well")
+    ap.add_argument("--pr_rows", type=int, default=50000, help="rows per side for --pr")
     a = ap.parse_args()
     import torch
     from otgan_amd.utils import inception_net, tfgraph
@@ -112,6 +118,36 @@ def main():
                     "kid_share_of_eval": round(kms / forward_ms_50000, 5), "kid_subsets": nsub, "kid_subset_size": m,
                     "kid_bank_rows": rows, "kid_features": "pool_3 of the graph" if a.batch >= m else "synthetic",
                     "pool3_channels": C, "kid_mean": float(v.mean()), "kid_std": float(v.std())})
+    if a.pr:
+        from otgan_amd.utils import kid, pr
+        C, n, K = plan.pool3_channels, a.pr_rows, 3
+        if a.batch >= n:
+            rows = [net.run(x, 127.5, 127.5)[0][:n], net.run(x.flip(0).neg(), 127.5, 127.5)[0][:n]]
+        else:       # non-negative, one scale per channel for both sides: the statistics of pool_3, not its values
+            scale = torch.rand((1, C), generator=g, device=dev)
+            rows = [torch.rand((n, C), generator=g, device=dev) * scale for _ in range(2)]
+        gen, real = (kid.FeatureBank(n, C, dev).append(r) for r in rows)
+        del rows
+
+        def passes():
+            return pr.precision_recall(gen, real, K, real_radii=pr.radii(real.rows, K))
+
+        for _ in range(min(a.warmup, 1)):
+            passes()
+        torch.cuda.synchronize()
+        reps = max(a.iters // 2, 1)                             # about a second per repetition at 50 000 rows
+        e0.record()
+        for _ in range(reps):
+            v = passes()
+        e1.record()
+        torch.cuda.synchronize()
+        pms = e0.elapsed_time(e1) / reps
+        out.update({"pr_ms": round(pms, 2), "pr_fp64_tflops": round(4 * 2.0 * n * n * C / (pms * 1e-3) / 1e12, 2),
+                    "pr_share_of_eval": round(pms / (ms * (50000 / a.batch)), 5), "pr_rows": n, "pr_neighbours": K, "pr_passes": 4,
+                    "pr_features": "pool_3 of the graph" if a.batch >= n else "synthetic", "pool3_channels": C,
+                    "pr_values": [round(f, 4) for f in v]})
+        if "kid_fp64_tflops" in out:
+            out["pr_rate_over_kid_rate"] = round(out["pr_fp64_tflops"] / out["kid_fp64_tflops"], 3)
     print(json.dumps(out))
 
 
