@@ -610,6 +610,9 @@ __global__ void adam_kernel(float* __restrict__ p, const float* __restrict__ g, 
 __global__ void adamax_kernel(float* __restrict__ p, const float* __restrict__ g,
                               float* __restrict__ v, float* __restrict__ mg, long n, float lr,
                               float mom1, float om1, float mom2) {
+  // (as adam_elem: the reference's graph rounds every product and sum; a fused `mom2 * mg + 1e-8f` or `p - lr * q` differs
+  // from it in the last bit -- tests/test_pointwise_edges_gpu.py holds all three optimisers to the same bit-exact emulation)
+#pragma clang fp contract(off)
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
     const float gi = g[i];
     float vt = gi;
@@ -624,6 +627,7 @@ __global__ void adamax_kernel(float* __restrict__ p, const float* __restrict__ g
 }
 __global__ void nesterov_kernel(float* __restrict__ p, const float* __restrict__ g,
                                 float* __restrict__ v, long n, float lr, float mom1, float opm) {
+#pragma clang fp contract(off)
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
     const float vo = v[i];
     const float vn = mom1 * vo - lr * g[i];            // nn.py:83

@@ -1492,7 +1492,9 @@ class GluFunction(torch.autograd.Function):
             ctx.save_for_backward(x)
             return pre
         y = torch.empty(x.shape[:-1] + (C2 // 2,), dtype=x.dtype, device=x.device)
-        rec = amax_slot(x.device) if (C2 // 2) % 4 == 0 else None
+        # the library writes a record from its float4 kernel only (C % 4 == 0, 16-byte aligned x and y); a contiguous view at
+        # an odd storage offset takes the scalar kernel and y goes on without one: its consumer reduces it (absmax_record)
+        rec = amax_slot(x.device) if (C2 // 2) % 4 == 0 and _aligned16(x, y) else None
         _lib.check(_lib.lib().otgan_glu_fwd_amax_f32(x.data_ptr(), rows, C2 // 2, y.data_ptr(), _lib.ptr(rec),
                                                      _lib.stream_ptr()), "glu_fwd")
         if rec is not None:
@@ -1506,7 +1508,7 @@ class GluFunction(torch.autograd.Function):
         dy = dy.contiguous()
         C2 = x.shape[-1]
         dx = torch.empty_like(x)
-        if (C2 // 2) % 4 == 0:
+        if (C2 // 2) % 4 == 0 and _aligned16(x, dy, dx):
             rec = amax_slot(x.device)
             # dx is the output gradient of the convolution in front of the GLU: leave its column sums (that layer's
             # bias gradient) with it instead of reading dx once more there
@@ -1518,6 +1520,8 @@ class GluFunction(torch.autograd.Function):
             leave(dx, "colsum", cs)
             tag_amax(dx, rec)
         else:
+            # scalar kernel (C % 4 != 0, or a misaligned contiguous view): dx carries neither; the convolution in front reduces
+            # its bias gradient and its record itself
             _lib.check(_lib.lib().otgan_glu_bwd_amax_f32(x.data_ptr(), dy.data_ptr(), x.numel() // C2,
                                                          C2 // 2, dx.data_ptr(), None, _lib.stream_ptr()), "glu_bwd")
         return dx
