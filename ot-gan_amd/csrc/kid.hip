@@ -3,43 +3,24 @@
 //     cubic kernel k(a, b) = (a.b / C + 1)^3,
 //       out[s][0] = sum_{i != j} k(X_i, X_j),   out[s][1] = sum_{i != j} k(Y_i, Y_j),   out[s][2] = sum_{i, j} k(X_i, Y_j).
 // The three Gram matrices are only ever summed, so none is written: a workgroup of four waves owns a 64 x 64 block of one
-// Gram (each wave 32 x 32 as 2 x 2 tiles of v_mfma_f64_16x16x4_f64), runs the channels in slabs of 32, applies the affine map
-// and the cube to its accumulators in registers and leaves ONE double.  As in moments.hip the fp32 inputs are converted to
-// fp64 BEFORE the multiply, so every product is exact; the dot products, the map, the cube and all sums are fp64.
+// Gram -- the block product of gram64.h (exact fp32 x fp32 products on the fp64 MFMA, operands through LDS) -- applies the
+// affine map and the cube to its accumulators in registers and leaves ONE double; the map, the cube and all sums are fp64.
 // Blocks: of the two symmetric Grams only the blocks on or above the diagonal exist.  A strictly upper block counts twice
 // (its mirror image is never computed); a diagonal block is computed whole -- both (i, j) and (j, i) of its pairs, once each
 // -- and drops i == j, BY POSITION in the index list: a row number that occurs twice is two rows.  The cross Gram has all
 // nb x nb blocks and no excluded diagonal.
-// Operands: unlike moments.hip (lanes of a tile = adjacent columns of x, coalesced) the lanes of a tile are different ROWS
-// here and K runs along the contiguous axis, so the gathered rows go through LDS: each thread fetches two 16-byte pieces
-// of the A rows and two of the B rows per slab (8 threads = the 128 contiguous bytes of one row), one slab ahead in
-// registers, into one of two LDS buffers (one barrier per slab).  A dot product may visit k in any order as long as A and
-// B agree, so the lane of k-group g = lane >> 4 takes the 8 CONSECUTIVE floats 8 g .. 8 g + 7 of its row of the slab (two
-// ds_read_b128) and step u of the slab multiplies k = 8 g + u: no scalar LDS reads.  Rows are 36 floats apart in LDS
-// (144 bytes): the 16 rows of a tile start in 16 different 16-byte slots of the 256-byte bank row; a ds_read_b128 lane
-// group mixes two k-groups, which leaves at most a 2-way conflict on a pair of its lanes -- 8 reads against 32 MFMAs of 16
-// passes each per slab and wave, the reads do not show.
-// Ragged edges: rows past m read row m - 1 of the list and channels past C read channel 0 (always valid addresses); the
-// channels are zeroed on the way into LDS and the rows are masked where the kernel value is summed.
+// Ragged edges: rows past m read row m - 1 of the list (gram64.h) and are masked where the kernel value is summed.
 // Deterministic: no atomics.  Lanes, waves and workgroups are added in a fixed order: the per-workgroup doubles go to
 // workspace[s][block] and a second launch adds the blocks of each (subset, output) in a fixed order.  A subset's value
 // does not depend on nsub or on its place in the call.
-// Operand layout of the f64 MFMA: lane l holds A[m = l & 15][k = l >> 4] and B[k = l >> 4][n = l & 15]; result register
-// r of lane l is D[m = (l >> 4) + 4 r][n = l & 15] -- NOT the row map of the f32 forms.
-#include "common.h"
+#include "gram64.h"
 #include "../../include/otgan.h"
 
 namespace {
 
-typedef double f64x4 __attribute__((ext_vector_type(4)));
-
-constexpr int kKidBlock = 64;    // rows and columns of a Gram per workgroup
-constexpr int kKidSlab = 32;     // channels per K slab
-constexpr int kKidLdsRow = 36;   // floats between rows of a slab in LDS
-
 // blocks per subset: nb (nb + 1) / 2 of each symmetric Gram and nb^2 of the cross Gram
 __host__ __device__ inline long kid_blocks(int m) {
-  const long nb = (m + kKidBlock - 1) / kKidBlock;
+  const long nb = (m + kGramBlock - 1) / kGramBlock;
   return nb * (nb + 1) + nb * nb;
 }
 
@@ -48,11 +29,11 @@ __host__ __device__ inline long kid_blocks(int m) {
 __global__ __launch_bounds__(256) void kid_block_kernel(int m, int C, const float* __restrict__ x, long ldx,
                                                         const int* __restrict__ xi, const float* __restrict__ y, long ldy,
                                                         const int* __restrict__ yi, double* __restrict__ partial) {
-  __shared__ __attribute__((aligned(16))) float lds[2][2][kKidBlock * kKidLdsRow];   // [buffer][A | B][row][k]
+  __shared__ __attribute__((aligned(16))) Gram64Lds lds;
   __shared__ double wave_part[4];
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, g = lane >> 4, c = lane & 15;
   const int s = blockIdx.y;
-  const int nb = (m + kKidBlock - 1) / kKidBlock, tri = nb * (nb + 1) / 2;
+  const int nb = (m + kGramBlock - 1) / kGramBlock, tri = nb * (nb + 1) / 2;
   int t = blockIdx.x, which, bi, bj;
   if (t < 2 * tri) {
     which = t < tri ? 0 : 1;
@@ -75,79 +56,19 @@ __global__ __launch_bounds__(256) void kid_block_kernel(int m, int C, const floa
   const int* aidx = (which == 1 ? yi : xi) + (long)s * m;
   const int* bidx = (which == 0 ? xi : yi) + (long)s * m;
 
-  // this thread's two 16-byte pieces of each operand: rows tid >> 3 and 32 + (tid >> 3) of the block, floats 4 q .. 4 q + 3
-  const int q = tid & 7, lrow = tid >> 3;
   const float* pa[2];
   const float* pb[2];
 #pragma unroll
   for (int u = 0; u < 2; ++u) {
-    const int ra = min(bi * kKidBlock + lrow + 32 * u, m - 1), rb = min(bj * kKidBlock + lrow + 32 * u, m - 1);
-    pa[u] = abase + (long)aidx[ra] * lda;
-    pb[u] = bbase + (long)bidx[rb] * ldb;
+    pa[u] = abase + (long)aidx[gram64_fetch_row(bi, u, m)] * lda;
+    pb[u] = bbase + (long)bidx[gram64_fetch_row(bj, u, m)] * ldb;
   }
-  f32x4 ra[2], rb[2];
-  auto fetch = [&](int k0) {
-    const int k = k0 + 4 * q;
-    const bool ok = k < C;          // C % 4 == 0: a piece is inside or outside as a whole
-    const int kc = ok ? k : 0;
-#pragma unroll
-    for (int u = 0; u < 2; ++u) {
-      const f32x4 va = *reinterpret_cast<const f32x4*>(pa[u] + kc), vb = *reinterpret_cast<const f32x4*>(pb[u] + kc);
-      const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
-      ra[u] = ok ? va : zero;
-      rb[u] = ok ? vb : zero;
-    }
-  };
-  auto stage = [&](int buf) {
-#pragma unroll
-    for (int u = 0; u < 2; ++u) {
-      *reinterpret_cast<f32x4*>(&lds[buf][0][(lrow + 32 * u) * kKidLdsRow + 4 * q]) = ra[u];
-      *reinterpret_cast<f32x4*>(&lds[buf][1][(lrow + 32 * u) * kKidLdsRow + 4 * q]) = rb[u];
-    }
-  };
-
-  // wave (wi, wj) owns rows 32 wi .. and columns 32 wj .. of the block; tile (ti, tj) register r of this lane is the
-  // element (32 wi + 16 ti + g + 4 r, 32 wj + 16 tj + c)
-  const int wi = wave >> 1, wj = wave & 1;
   f64x4 acc[2][2];
-#pragma unroll
-  for (int ti = 0; ti < 2; ++ti)
-#pragma unroll
-    for (int tj = 0; tj < 2; ++tj)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) acc[ti][tj][r] = 0.0;
+  gram64_block_product(C, pa, pb, lds, acc);
 
-  const int slabs = (C + kKidSlab - 1) / kKidSlab;
-  fetch(0);
-  stage(0);
-  __syncthreads();
-  for (int sl = 0; sl < slabs; ++sl) {
-    const int buf = sl & 1;
-    if (sl + 1 < slabs) fetch((sl + 1) * kKidSlab);
-    f32x4 fa[2][2], fb[2][2];      // [tile][half]: floats 8 g + 4 half .. of row 16 tile + c
-#pragma unroll
-    for (int tt = 0; tt < 2; ++tt)
-#pragma unroll
-      for (int h = 0; h < 2; ++h) {
-        fa[tt][h] = *reinterpret_cast<const f32x4*>(&lds[buf][0][(32 * wi + 16 * tt + c) * kKidLdsRow + 8 * g + 4 * h]);
-        fb[tt][h] = *reinterpret_cast<const f32x4*>(&lds[buf][1][(32 * wj + 16 * tt + c) * kKidLdsRow + 8 * g + 4 * h]);
-      }
-#pragma unroll
-    for (int h = 0; h < 2; ++h)
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const double a0 = (double)fa[0][h][e], a1 = (double)fa[1][h][e];
-        const double b0 = (double)fb[0][h][e], b1 = (double)fb[1][h][e];
-        acc[0][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, b0, acc[0][0], 0, 0, 0);
-        acc[0][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, b1, acc[0][1], 0, 0, 0);
-        acc[1][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b0, acc[1][0], 0, 0, 0);
-        acc[1][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b1, acc[1][1], 0, 0, 0);
-      }
-    if (sl + 1 < slabs) stage(buf ^ 1);      // (the buffer the slab before this one was read from: every wave is past it)
-    __syncthreads();
-  }
-
-  // k = (g / C + 1)^3 of the counted pairs, added in a fixed order: registers, lanes (xor tree), waves
+  // k = (g / C + 1)^3 of the counted pairs, added in a fixed order: registers, lanes (xor tree), waves; tile (ti, tj)
+  // register r of this lane is the element (32 wi + 16 ti + g + 4 r, 32 wj + 16 tj + c) of the block
+  const int wi = wave >> 1, wj = wave & 1;
   const double dC = (double)C;
   const bool drop_diag = which < 2;        // (i == j occurs in diagonal blocks only)
   double sum = 0.0;
@@ -157,7 +78,7 @@ __global__ __launch_bounds__(256) void kid_block_kernel(int m, int C, const floa
     for (int tj = 0; tj < 2; ++tj)
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
-        const int i = bi * kKidBlock + 32 * wi + 16 * ti + g + 4 * r, j = bj * kKidBlock + 32 * wj + 16 * tj + c;
+        const int i = bi * kGramBlock + 32 * wi + 16 * ti + g + 4 * r, j = bj * kGramBlock + 32 * wj + 16 * tj + c;
         const double v = acc[ti][tj][r] / dC + 1.0;
         const bool counted = i < m && j < m && !(drop_diag && i == j);
         sum += counted ? v * v * v : 0.0;
@@ -175,7 +96,7 @@ __global__ __launch_bounds__(256) void kid_block_kernel(int m, int C, const floa
 // order, then the xor tree over the lanes
 __global__ __launch_bounds__(192) void kid_reduce_kernel(int m, const double* __restrict__ partial, double* __restrict__ out) {
   const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const long nb = (m + kKidBlock - 1) / kKidBlock, tri = nb * (nb + 1) / 2, total = 2 * tri + nb * nb;
+  const long nb = (m + kGramBlock - 1) / kGramBlock, tri = nb * (nb + 1) / 2, total = 2 * tri + nb * nb;
   const long lo = w * tri, hi = w == 2 ? total : lo + tri;
   const double* p = partial + (long)blockIdx.x * total;
   double sum = 0.0;

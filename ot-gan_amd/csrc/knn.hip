@@ -4,8 +4,7 @@
 //       inside[i]          = #{ j : d2(q_i, y_j) <= thresh[j] },
 //     with d2(a, b) = max(0, (n_a + n_b) - 2 a.b) and n_x = x.x.
 // The distance matrix is never written: as in kid.hip a workgroup of four waves forms a 64 x 64 block of the Gram matrix
-// (each wave 32 x 32 as 2 x 2 tiles of v_mfma_f64_16x16x4_f64, the channels in slabs of 32 through two LDS buffers, the
-// fp32 inputs converted to fp64 BEFORE the multiply so every product is exact) and the epilogue differs: a workgroup
+// with the block product of gram64.h (exact fp32 x fp32 products on the fp64 MFMA) and the epilogue differs: a workgroup
 // keeps its 64 query rows, walks the column blocks of its share of the columns, and after each block every lane folds
 // its 8 rows x 2 columns of distances into 8 sorted lists and 8 counters, all in registers (a compare-exchange chain of
 // v_min_f64 / v_max_f64 with static indices: 16 values x KL steps per block and lane against 2048 MFMAs per block and
@@ -13,32 +12,22 @@
 // with the 32 of the accumulators leave one workgroup per CU; lists of 4 leave two, as the usual k = 3 wants.  The
 // lists of the 32 lanes that share a row (16 lanes x the 2 waves of a block row) are merged ONCE, after the last column
 // block: an xor tree over the lanes, then LDS over the two waves.
-// One bit pattern per pair: every element of every block, whichever kernel, tile, lane or operand side it is in, adds
-// the products of its pair in the same order -- slab by slab, step u = 0 .. 7 of a slab adds channels u, 8 + u, 16 + u,
-// 24 + u in one MFMA, channels past C as zeros -- so a.b depends on (a, b, C) only and a.b == b.a; the norms are the
-// DIAGONAL of the same block product (knn_norm_kernel), so n_x == x.x of that order and d2(a, a) == 0 exactly; n_a + n_b
-// commutes.  A k-smallest list is a multiset and a count an integer, so the outputs depend neither on the order of the
+// One bit pattern per pair: a.b depends on (a, b, C) only and a.b == b.a, because every kernel here and in kid.hip runs
+// the one loop of gram64.h (the order of additions: there); the norms are the DIAGONAL of the same block product
+// (knn_norm_kernel), so n_x == x.x of that order and d2(a, a) == 0 exactly; n_a + n_b commutes.  A k-smallest list is a multiset and a count an integer, so the outputs depend neither on the order of the
 // columns nor on their split over workgroups.
 // Column split: with few query blocks the column blocks are split over blockIdx.y (knn_plan: about 1024 workgroups, at
 // least 4 column blocks each); every (split, row) leaves k doubles and one count in the workspace and a second launch
 // merges the splits of each row -- always, also for one split.  No atomics.  Workspace: the norms of q and y, then
 // [splits][nq][k] doubles, then [splits][nq] counts.
-// Ragged edges: rows past the end read the last row (a valid address) and are masked where the distances are folded;
-// channels past C read channel 0 and are zeroed on the way into LDS.
-// Operand layout of the f64 MFMA: lane l holds A[m = l & 15][k = l >> 4] and B[k = l >> 4][n = l & 15]; result register
-// r of lane l is D[m = (l >> 4) + 4 r][n = l & 15] -- NOT the row map of the f32 forms.
+// Ragged edges: rows past the end read the last row (gram64.h) and are masked where the distances are folded.
 #include <limits>
 
-#include "common.h"
+#include "gram64.h"
 #include "../../include/otgan.h"
 
 namespace {
 
-typedef double f64x4 __attribute__((ext_vector_type(4)));
-
-constexpr int kKnnBlock = 64;    // query rows and columns per block
-constexpr int kKnnSlab = 32;     // channels per K slab
-constexpr int kKnnLdsRow = 36;   // floats between rows of a slab in LDS (kid.hip: 16 rows of a tile in 16 different slots)
 constexpr int kKnnMaxK = 8;      // length of the register lists
 constexpr int kKnnMinPer = 4;    // fewest column blocks a split is worth
 constexpr int kKnnGroups = 1024; // workgroups the column split aims at
@@ -49,8 +38,8 @@ struct KnnPlan {
 
 inline KnnPlan knn_plan(int nq, int ny) {
   KnnPlan p;
-  p.nbq = (nq + kKnnBlock - 1) / kKnnBlock;
-  p.nbc = (ny + kKnnBlock - 1) / kKnnBlock;
+  p.nbq = (nq + kGramBlock - 1) / kGramBlock;
+  p.nbc = (ny + kGramBlock - 1) / kGramBlock;
   p.per = p.splits = 0;
   if (p.nbq == 0 || p.nbc == 0) return p;
   const int want = (kKnnGroups + p.nbq - 1) / p.nbq;
@@ -58,74 +47,6 @@ inline KnnPlan knn_plan(int nq, int ny) {
   if (p.per < kKnnMinPer) p.per = kKnnMinPer;
   p.splits = (p.nbc + p.per - 1) / p.per;
   return p;
-}
-
-typedef float KnnLds[2][2][kKnnBlock * kKnnLdsRow];   // [buffer][A | B][row][k]
-
-// acc = A B^T of the 64 rows at pa (this thread's two 16-byte pieces: rows tid >> 3 and 32 + (tid >> 3), floats
-// 4 (tid & 7) ...) and the 64 rows at pb, all C channels.  Wave (wi, wj) owns rows 32 wi .. and columns 32 wj .. of the
-// block; tile (ti, tj) register r of a lane is the element (32 wi + 16 ti + g + 4 r, 32 wj + 16 tj + c).  The loop of
-// kid.hip.  Ends after a barrier: LDS is free again.
-__device__ __forceinline__ void knn_block_product(int C, const float* const (&pa)[2], const float* const (&pb)[2],
-                                                  KnnLds& lds, f64x4 (&acc)[2][2]) {
-  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, g = lane >> 4, c = lane & 15;
-  const int q = tid & 7, lrow = tid >> 3, wi = wave >> 1, wj = wave & 1;
-  f32x4 ra[2], rb[2];
-  auto fetch = [&](int k0) {
-    const int k = k0 + 4 * q;
-    const bool ok = k < C;          // C % 4 == 0: a piece is inside or outside as a whole
-    const int kc = ok ? k : 0;
-#pragma unroll
-    for (int u = 0; u < 2; ++u) {
-      const f32x4 va = *reinterpret_cast<const f32x4*>(pa[u] + kc), vb = *reinterpret_cast<const f32x4*>(pb[u] + kc);
-      const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
-      ra[u] = ok ? va : zero;
-      rb[u] = ok ? vb : zero;
-    }
-  };
-  auto stage = [&](int buf) {
-#pragma unroll
-    for (int u = 0; u < 2; ++u) {
-      *reinterpret_cast<f32x4*>(&lds[buf][0][(lrow + 32 * u) * kKnnLdsRow + 4 * q]) = ra[u];
-      *reinterpret_cast<f32x4*>(&lds[buf][1][(lrow + 32 * u) * kKnnLdsRow + 4 * q]) = rb[u];
-    }
-  };
-#pragma unroll
-  for (int ti = 0; ti < 2; ++ti)
-#pragma unroll
-    for (int tj = 0; tj < 2; ++tj)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) acc[ti][tj][r] = 0.0;
-
-  const int slabs = (C + kKnnSlab - 1) / kKnnSlab;
-  fetch(0);
-  stage(0);
-  __syncthreads();
-  for (int sl = 0; sl < slabs; ++sl) {
-    const int buf = sl & 1;
-    if (sl + 1 < slabs) fetch((sl + 1) * kKnnSlab);
-    f32x4 fa[2][2], fb[2][2];      // [tile][half]: floats 8 g + 4 half .. of row 16 tile + c
-#pragma unroll
-    for (int tt = 0; tt < 2; ++tt)
-#pragma unroll
-      for (int h = 0; h < 2; ++h) {
-        fa[tt][h] = *reinterpret_cast<const f32x4*>(&lds[buf][0][(32 * wi + 16 * tt + c) * kKnnLdsRow + 8 * g + 4 * h]);
-        fb[tt][h] = *reinterpret_cast<const f32x4*>(&lds[buf][1][(32 * wj + 16 * tt + c) * kKnnLdsRow + 8 * g + 4 * h]);
-      }
-#pragma unroll
-    for (int h = 0; h < 2; ++h)
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const double a0 = (double)fa[0][h][e], a1 = (double)fa[1][h][e];
-        const double b0 = (double)fb[0][h][e], b1 = (double)fb[1][h][e];
-        acc[0][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, b0, acc[0][0], 0, 0, 0);
-        acc[0][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, b1, acc[0][1], 0, 0, 0);
-        acc[1][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b0, acc[1][0], 0, 0, 0);
-        acc[1][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b1, acc[1][1], 0, 0, 0);
-      }
-    if (sl + 1 < slabs) stage(buf ^ 1);      // (the buffer the slab before this one was read from: every wave is past it)
-    __syncthreads();
-  }
 }
 
 // v into the ascending list, the largest of the KL + 1 falls out
@@ -144,10 +65,10 @@ __device__ __forceinline__ void knn_insert(double (&list)[KL], double v) {
 __global__ __launch_bounds__(256) void knn_norm_kernel(int nq, int ny, int C, const float* __restrict__ q, long ldq,
                                                        const float* __restrict__ y, long ldy, double* __restrict__ normq,
                                                        double* __restrict__ normy) {
-  __shared__ __attribute__((aligned(16))) KnnLds lds;
+  __shared__ __attribute__((aligned(16))) Gram64Lds lds;
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, g = lane >> 4, c = lane & 15;
-  const int wi = wave >> 1, wj = wave & 1, lrow = tid >> 3;
-  const int nbq = (nq + kKnnBlock - 1) / kKnnBlock;
+  const int wi = wave >> 1, wj = wave & 1;
+  const int nbq = (nq + kGramBlock - 1) / kGramBlock;
   const bool second = (int)blockIdx.x >= nbq;
   const int b = second ? blockIdx.x - nbq : blockIdx.x, n = second ? ny : nq;
   const float* x = second ? y : q;
@@ -155,15 +76,15 @@ __global__ __launch_bounds__(256) void knn_norm_kernel(int nq, int ny, int C, co
   double* norm = second ? normy : normq;
   const float* p[2];
 #pragma unroll
-  for (int u = 0; u < 2; ++u) p[u] = x + (long)min(b * kKnnBlock + lrow + 32 * u, n - 1) * ld;
+  for (int u = 0; u < 2; ++u) p[u] = x + (long)gram64_fetch_row(b, u, n) * ld;
   f64x4 acc[2][2];
-  knn_block_product(C, p, p, lds, acc);
+  gram64_block_product(C, p, p, lds, acc);
   if (wi != wj) return;
 #pragma unroll
   for (int ti = 0; ti < 2; ++ti)
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
-      const int i = b * kKnnBlock + 32 * wi + 16 * ti + g + 4 * r;
+      const int i = b * kGramBlock + 32 * wi + 16 * ti + g + 4 * r;
       if (g + 4 * r == c && i < n) norm[i] = acc[ti][ti][r];
     }
 }
@@ -175,18 +96,18 @@ __global__ __launch_bounds__(256, KL <= 4 ? 2 : 1) void knn_block_kernel(int nq,
                                                         const double* __restrict__ normq, const double* __restrict__ normy,
                                                         const double* __restrict__ thresh, int per,
                                                         double* __restrict__ part, int* __restrict__ cnt) {
-  __shared__ __attribute__((aligned(16))) KnnLds lds;
-  __shared__ double wave_list[2][kKnnBlock][KL];     // [wj][row of the block][entry]
-  __shared__ int wave_cnt[2][kKnnBlock];
+  __shared__ __attribute__((aligned(16))) Gram64Lds lds;
+  __shared__ double wave_list[2][kGramBlock][KL];     // [wj][row of the block][entry]
+  __shared__ int wave_cnt[2][kGramBlock];
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, g = lane >> 4, c = lane & 15;
-  const int wi = wave >> 1, wj = wave & 1, lrow = tid >> 3;
-  const int bi = blockIdx.x, nbc = (ny + kKnnBlock - 1) / kKnnBlock;
+  const int wi = wave >> 1, wj = wave & 1;
+  const int bi = blockIdx.x, nbc = (ny + kGramBlock - 1) / kGramBlock;
   const int jb0 = blockIdx.y * per, jb1 = min(jb0 + per, nbc);
   const double inf = std::numeric_limits<double>::infinity();
 
   const float* pa[2];
 #pragma unroll
-  for (int u = 0; u < 2; ++u) pa[u] = q + (long)min(bi * kKnnBlock + lrow + 32 * u, nq - 1) * ldq;
+  for (int u = 0; u < 2; ++u) pa[u] = q + (long)gram64_fetch_row(bi, u, nq) * ldq;
 
   // slot s = 4 ti + r of this lane is row 32 wi + 16 ti + g + 4 r of the block
   double list[8][KL], nrow[8];
@@ -195,7 +116,7 @@ __global__ __launch_bounds__(256, KL <= 4 ? 2 : 1) void knn_block_kernel(int nq,
   bool rowok[8];
 #pragma unroll
   for (int s = 0; s < 8; ++s) {
-    const int i = bi * kKnnBlock + 32 * wi + 16 * (s >> 2) + g + 4 * (s & 3);
+    const int i = bi * kGramBlock + 32 * wi + 16 * (s >> 2) + g + 4 * (s & 3);
     rowok[s] = i < nq;
     nrow[s] = normq[min(i, nq - 1)];
     selfj[s] = self0 >= 0 ? (long)self0 + i : -1L;          // (no column has number -1)
@@ -207,14 +128,14 @@ __global__ __launch_bounds__(256, KL <= 4 ? 2 : 1) void knn_block_kernel(int nq,
   for (int jb = jb0; jb < jb1; ++jb) {
     const float* pb[2];
 #pragma unroll
-    for (int u = 0; u < 2; ++u) pb[u] = y + (long)min(jb * kKnnBlock + lrow + 32 * u, ny - 1) * ldy;
+    for (int u = 0; u < 2; ++u) pb[u] = y + (long)gram64_fetch_row(jb, u, ny) * ldy;
     f64x4 acc[2][2];
-    knn_block_product(C, pa, pb, lds, acc);
+    gram64_block_product(C, pa, pb, lds, acc);
     int j[2];
     double ncol[2], th[2];
 #pragma unroll
     for (int tj = 0; tj < 2; ++tj) {
-      j[tj] = jb * kKnnBlock + 32 * wj + 16 * tj + c;
+      j[tj] = jb * kGramBlock + 32 * wj + 16 * tj + c;
       const int jc = min(j[tj], ny - 1);
       ncol[tj] = normy[jc];
       th[tj] = thresh ? thresh[jc] : 0.0;
@@ -253,8 +174,8 @@ __global__ __launch_bounds__(256, KL <= 4 ? 2 : 1) void knn_block_kernel(int nq,
   }
   __syncthreads();
   // the two waves of a block row, one thread per row
-  const int i = bi * kKnnBlock + tid;
-  if (tid < kKnnBlock && i < nq) {
+  const int i = bi * kGramBlock + tid;
+  if (tid < kGramBlock && i < nq) {
     double m[KL];
 #pragma unroll
     for (int t = 0; t < KL; ++t) m[t] = wave_list[0][tid][t];

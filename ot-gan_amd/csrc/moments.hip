@@ -8,14 +8,12 @@
 // nothing is an atomic: the same sequence of calls gives the same bits.  Every element on or above the diagonal is
 // stored to [i][j] and to [j][i], and of a diagonal tile only the elements with i <= j are: `outer` is exactly symmetric.
 // The waves of the diagonal blocks also own the column sums of their 32 columns.
-// Operand layout of the f64 MFMA: lane l holds A[m = l & 15][k = l >> 4] and B[k = l >> 4][n = l & 15]; result register
-// r of lane l is D[m = (l >> 4) + 4 r][n = l & 15] -- NOT the row map of the f32 forms.
-#include "common.h"
+// Operand layout of the f64 MFMA: gram64.h, which also has the f64x4 type (its LDS-staged block product is another
+// algorithm: here the lanes of a tile are adjacent columns of x and nothing goes through LDS).
+#include "gram64.h"
 #include "../../include/otgan.h"
 
 namespace {
-
-typedef double f64x4 __attribute__((ext_vector_type(4)));
 
 constexpr int kMomBlock = 32;   // columns of `outer` per wave and side
 

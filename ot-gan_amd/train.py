@@ -126,61 +126,50 @@ def inception_hook(model, args, classifier, state, rank=0, world=1):
     the class probabilities are gathered, so no rank waits at the next epoch's first collective while rank 0 alone
     samples and scores 2 x 50 000 images.  All ranks get the same scores; rank 0 prints them.
 
-    With the real data's pool_3 statistics in `state["fid_real"]` = (mu, sigma) (--fid_stats; device classifier only) the
-    same forward pass also feeds the Frechet Inception Distance (utils/fid.py): pool_3 of exactly the `eval_samples`
-    samples the score covers goes into fp64 moments on the device, one SUM all-reduce per evaluated model replaces a
-    feature gather, rank 0 finalises on the host and broadcasts the scalar.
-
-    With --kid_subsets > 0 and the real data's features in `state["kid_real"]` (a utils.kid.FeatureBank; device classifier
-    only) the same pool_3 rows -- this rank's `mine` rows that survive the cut to `eval_samples` -- also fill a feature
-    bank on the device, and the Kernel Inception Distance (utils/kid.py) of every evaluated model is reported as
-    (mean, std) over the subsets: one fused kernel-sum launch per rank, one small all-reduce.
-
-    With --pr_neighbours K > 0 and `state["pr_real"]` / `state["pr_real_radii"]` (real_pr_state; device classifier only) the
-    same bank -- filled when either KID or this is on -- also gives (precision, recall, density, coverage) of every
-    evaluated model (utils/pr.py): three fused k-NN passes, the same values for every world size."""
+    With the device classifier the same forward pass also feeds the metrics on pool_3 (utils.features.HookMetric), each
+    on pool_3 of exactly the `eval_samples` samples the score covers -- this rank's `mine` rows that survive the cut:
+    the Frechet Inception Distance with `state["fid_real"]` = (mu, sigma) (--fid_stats; fid.FidMetric), the Kernel
+    Inception Distance with --kid_subsets > 0 and `state["kid_real"]` (real_kid_state; kid.KidMetric), and precision,
+    recall, density and coverage with --pr_neighbours > 0 and `state["pr_real"]` / `state["pr_real_radii"]`
+    (real_pr_state; pr.PrMetric).  The last two read the rows from one device feature bank, `state["kid_gen"]`, which
+    is filled when either is on: allocated once per run, cleared per model."""
     from .utils.inception import class_probabilities, inception_score_from_probs
+    from .utils import features
     from . import parallel
     on_device = hasattr(classifier, "probs_from_generator")    # utils.inception_net.InceptionNet: samples stay on the GPU
-    fid_real = state.get("fid_real") if on_device else None
-    share = -(-args.eval_samples // world)
+    share = features.share(args.eval_samples, 0, world)[1]     # every rank draws as many as rank 0 holds
     # the gather below is cut to eval_samples rows: of this rank's share the first `mine` survive
-    mine = min(max(args.eval_samples - rank * share, 0), share)
-    kid_real = state.get("kid_real") if on_device and getattr(args, "kid_subsets", 0) > 0 else None
-    pr_k = getattr(args, "pr_neighbours", 0)
-    pr_real = state.get("pr_real") if on_device and pr_k > 0 else None
-    out = {}
-    if fid_real is not None:
-        from .utils import fid
-        state.setdefault("fid_min", float("inf"))
-        state.setdefault("fid_iter", 0)
-    if kid_real is not None:
-        from .utils import kid
-        state.setdefault("kid_min", float("inf"))
-        state.setdefault("kid_iter", 0)
-        if "kid_m" not in state:
-            state["kid_m"] = kid.effective_subset_size(args.kid_subset_size, args.eval_samples, kid_real.total, world)
-    if pr_real is not None:
-        from .utils import kid, pr
-    if kid_real is not None or pr_real is not None:
+    lo, hi = features.share(args.eval_samples, rank, world)
+    mine = hi - lo
+    metrics = []
+    if on_device:       # each metric is on with its flag and what its real_*_state left in `state`
+        from .utils import fid, kid, pr
+        for cls, flag in ((fid.FidMetric, True), (kid.KidMetric, getattr(args, "kid_subsets", 0) > 0),
+                          (pr.PrMetric, getattr(args, "pr_neighbours", 0) > 0)):
+            if flag and state.get(cls.key + "_real") is not None:
+                metrics.append(cls(state[cls.key + "_real"], args, classifier, state, rank, world))
+    bank = None
+    if any(m.uses_bank for m in metrics):
         if "kid_gen" not in state or state["kid_gen"].buf.shape[0] < mine:      # one buffer for every evaluation of the run
-            state["kid_gen"] = kid.FeatureBank(mine, classifier.plan.pool3_channels, classifier.device, total=args.eval_samples)
+            state["kid_gen"] = features.FeatureBank(mine, classifier.plan.pool3_channels, classifier.device, total=args.eval_samples)
+        bank = state["kid_gen"]
+    out = {}
     for tag, ema in (("", False), ("EMA ", True)):
         probs, have = [], 0
-        if fid_real is not None:
-            acc = fid.MomentAccumulator(classifier.plan.pool3_channels, classifier.device)
-        if kid_real is not None or pr_real is not None:
-            state["kid_gen"].clear()
+        for m in metrics:
+            m.begin()
+        if bank is not None:
+            bank.clear()
         while have < share:
             x = model.sample(min(1000, share - have), ema=ema)
-            if fid_real is not None or kid_real is not None or pr_real is not None:
+            if metrics:
                 p, pool3 = classifier.probs_and_pool3_from_generator(x.float())
                 probs.append(p)
                 kept = pool3[:min(max(mine - have, 0), x.shape[0])]
-                if fid_real is not None:
-                    acc.update(kept)
-                if kid_real is not None or pr_real is not None:
-                    state["kid_gen"].append(kept)
+                for m in metrics:
+                    m.take(kept)
+                if bank is not None:
+                    bank.append(kept)
             elif on_device:
                 probs.append(classifier.probs_from_generator(x.float()))                      # 127.5 (x + 1) folded in
             else:
@@ -198,34 +187,12 @@ def inception_hook(model, args, classifier, state, rank=0, world=1):
         if score[0] > state["max"]:
             state["max"], state["iter"] = score[0], state["epoch"]
         out[tag.strip() or "live"] = score
-        if fid_real is not None:
-            acc.all_reduce()
-            d = torch.zeros(1, dtype=torch.float64, device=classifier.device)
-            if rank == 0:
-                d[0] = fid.frechet_distance(*fid.stats_from_moments(*acc.moments()), fid_real[0], fid_real[1])
-                print('%sFID was %.4f' % (tag, float(d)))
-            d = float(parallel.broadcast_(d))
-            if d < state.get("fid_min", float("inf")):
-                state["fid_min"], state["fid_iter"] = d, state["epoch"]
-            out["fid_" + (tag.strip() or "live")] = d
-        if kid_real is not None:
-            k = kid.kid(state["kid_gen"], kid_real, args.kid_subsets, state["kid_m"], getattr(args, "seed", 1), rank, world)
-            if rank == 0:
-                print('%sKID was %.6f, std was %.6f' % (tag, k[0], k[1]))
-            if k[0] < state["kid_min"]:
-                state["kid_min"], state["kid_iter"] = k[0], state["epoch"]
-            out["kid_" + (tag.strip() or "live")] = k
-        if pr_real is not None:
-            v = pr.precision_recall(state["kid_gen"], pr_real, pr_k, state["pr_real_radii"], rank, world)
-            if rank == 0:
-                print('%sprecision was %.4f, recall was %.4f, density was %.4f, coverage was %.4f' % ((tag,) + v))
-            out["pr_" + (tag.strip() or "live")] = v
+        for m in metrics:
+            out[m.key + "_" + (tag.strip() or "live")] = m.finish(tag, bank)
     if rank == 0:
         print('max inception score was %.6f, iter was %d' % (state["max"], state["iter"]))
-        if fid_real is not None:
-            print('min FID was %.4f, iter was %d' % (state["fid_min"], state["fid_iter"]))
-        if kid_real is not None:
-            print('min KID was %.6f, iter was %d' % (state["kid_min"], state["kid_iter"]))
+    for m in metrics:
+        m.close()
     return out
 
 
@@ -235,9 +202,7 @@ def real_fid_stats(args, classifier, trainx, rank=0, world=1):
     the classifier is not the device network of the 2015 graph: FID is defined on its pool_3."""
     from . import parallel
     from .utils import fid
-    if not hasattr(classifier, "probs_and_pool3_from_generator"):
-        if rank == 0:
-            print('--fid_stats: FID needs the 2015 Inception graph as --inception_model (it is defined on its pool_3); skipped')
+    if not _has_pool3(classifier, rank, '--fid_stats: FID needs', 'it is'):
         return None
     C = classifier.plan.pool3_channels
     there = torch.tensor([1.0 if os.path.exists(args.fid_stats) else 0.0], device=classifier.device)
@@ -246,15 +211,43 @@ def real_fid_stats(args, classifier, trainx, rank=0, world=1):
         if rank == 0:
             print('FID statistics of the real data: loaded %s (%s)' % (args.fid_stats, '%d images' % n if n else 'n not recorded'))
         return mu, sigma
-    if not args.fid_real_samples:
-        x = trainx
-    else:       # (a utils.data.DeviceDataset has no slices: `head` shares its store)
-        x = trainx.head(args.fid_real_samples) if hasattr(trainx, "head") else trainx[:args.fid_real_samples]
+    x = _head(trainx, args.fid_real_samples) if args.fid_real_samples else trainx
     mu, sigma, n = fid.dataset_stats(classifier, x, rank, world)
     if rank == 0:
         fid.save_stats(args.fid_stats, mu, sigma, n)
         print('FID statistics of the real data: computed from %d training images, saved to %s' % (n, args.fid_stats))
     return mu, sigma
+
+
+def _has_pool3(classifier, rank, needs, they_are):
+    """Is the classifier the device network of the 2015 graph, whose pool_3 the metrics are defined on?  If not, rank 0
+    says so once."""
+    ok = hasattr(classifier, "probs_and_pool3_from_generator")
+    if not ok and rank == 0:
+        print('%s the 2015 Inception graph as --inception_model (%s defined on its pool_3); skipped' % (needs, they_are))
+    return ok
+
+
+def _head(trainx, n):
+    """the first n training images (a utils.data.DeviceDataset has no slices: `head` shares its store)"""
+    return trainx.head(n) if hasattr(trainx, "head") else trainx[:n]
+
+
+def _real_features(args, classifier, trainx, rank, world, needs, they_are, samples, check, what, reuse=None):
+    """The real side of a metric on feature banks: (pool_3 of the first `samples or eval_samples` training images as this
+    rank's share of a device feature bank -- `reuse` when that bank holds the same images --, check(images)), or None
+    when the classifier has no pool_3.  `check` raises, and says what it has to say, before anything is classified."""
+    from .utils import features
+    if not _has_pool3(classifier, rank, needs, they_are):
+        return None
+    n = min(samples or args.eval_samples, trainx.shape[0])
+    checked = check(n)
+    shared = reuse is not None and reuse.total == n
+    bank = reuse if shared else features.real_bank(classifier, _head(trainx, n), n, rank, world)
+    if rank == 0:
+        print('%s features of the real data: pool_3 of the first %d training images, %s (%.1f MB per rank)'
+              % (what, n, 'the bank KID keeps' if shared else 'kept on the device', bank.buf.numel() * 4 / 1e6))
+    return bank, checked
 
 
 def real_kid_state(args, classifier, trainx, rank=0, world=1):
@@ -263,21 +256,16 @@ def real_kid_state(args, classifier, trainx, rank=0, world=1):
     effect}.  Empty (said once) when the classifier is not the device network of the 2015 graph.  A subset size below 2
     is a ValueError before anything is classified."""
     from .utils import kid
-    if not hasattr(classifier, "probs_and_pool3_from_generator"):
-        if rank == 0:
-            print('--kid_subsets: KID needs the 2015 Inception graph as --inception_model (it is defined on its pool_3); skipped')
-        return {}
-    n = min(args.kid_real_samples or args.eval_samples, trainx.shape[0])
-    m = kid.effective_subset_size(args.kid_subset_size, args.eval_samples, n, world)
-    if rank == 0 and m < args.kid_subset_size:
-        print('KID subsets hold %d rows, not --kid_subset_size %d: the smallest rank has no more generated or real rows'
-              % (m, args.kid_subset_size))
-    x = trainx.head(n) if hasattr(trainx, "head") else trainx[:n]      # (a utils.data.DeviceDataset has no slices)
-    bank = kid.real_bank(classifier, x, n, rank, world)
-    if rank == 0:
-        print('KID features of the real data: pool_3 of the first %d training images, kept on the device (%.1f MB per rank)'
-              % (n, bank.buf.numel() * 4 / 1e6))
-    return {"kid_real": bank, "kid_m": m}
+
+    def subset_size(n):
+        m = kid.effective_subset_size(args.kid_subset_size, args.eval_samples, n, world)
+        if rank == 0 and m < args.kid_subset_size:
+            print('KID subsets hold %d rows, not --kid_subset_size %d: the smallest rank has no more generated or real rows'
+                  % (m, args.kid_subset_size))
+        return m
+    made = _real_features(args, classifier, trainx, rank, world, '--kid_subsets: KID needs', 'it is', args.kid_real_samples,
+                          subset_size, 'KID')
+    return {"kid_real": made[0], "kid_m": made[1]} if made else {}
 
 
 def real_pr_state(args, classifier, trainx, rank=0, world=1, kid_bank=None):
@@ -286,24 +274,11 @@ def real_pr_state(args, classifier, trainx, rank=0, world=1, kid_bank=None):
     bank KID keeps, when that holds the same images), "pr_real_radii": the K-th neighbour radius of every real row over
     all ranks, computed once}.  Empty (said once) when the classifier is not the device network of the 2015 graph.  A
     side with no more than K rows is a ValueError before anything is classified."""
-    from .utils import kid, pr
-    if not hasattr(classifier, "probs_and_pool3_from_generator"):
-        if rank == 0:
-            print('--pr_neighbours: precision and recall need the 2015 Inception graph as --inception_model (they are defined '
-                  'on its pool_3); skipped')
-        return {}
-    n = min(args.pr_real_samples or args.eval_samples, trainx.shape[0])
-    k = pr.check_neighbours(args.pr_neighbours, args.eval_samples, n)
-    shared = kid_bank is not None and kid_bank.total == n
-    if shared:
-        bank = kid_bank
-    else:
-        x = trainx.head(n) if hasattr(trainx, "head") else trainx[:n]      # (a utils.data.DeviceDataset has no slices)
-        bank = kid.real_bank(classifier, x, n, rank, world)
-    if rank == 0:
-        print('precision / recall features of the real data: pool_3 of the first %d training images, %s (%.1f MB per rank)'
-              % (n, 'the bank KID keeps' if shared else 'kept on the device', bank.buf.numel() * 4 / 1e6))
-    return {"pr_real": bank, "pr_real_radii": pr.radii(bank.rows, k, rank, world)}
+    from .utils import pr
+    made = _real_features(args, classifier, trainx, rank, world, '--pr_neighbours: precision and recall need', 'they are',
+                          args.pr_real_samples, lambda n: pr.check_neighbours(args.pr_neighbours, args.eval_samples, n),
+                          'precision / recall', kid_bank)
+    return {"pr_real": made[0], "pr_real_radii": pr.radii(made[0].rows, made[1], rank, world)} if made else {}
 
 
 def load_cifar(data_dir, subset='train'):

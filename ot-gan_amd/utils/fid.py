@@ -23,6 +23,7 @@ files, which therefore load as they are -- plus the sample count `n`.
 import numpy as np
 
 from .. import _lib
+from . import features
 
 
 class MomentAccumulator:
@@ -128,25 +129,39 @@ def load_stats(path, C):
 
 
 def dataset_stats(classifier, images, rank=0, world=1):
-    """(mu, sigma, n) of pool_3 over `images` -- numpy [N, H, W, 3] in [-1, 1], the form of train.py's `trainx`, or a
-    `utils.data.DeviceDataset`, read through its `rows` (the same floats, converted on the device).
-    Rank r classifies the contiguous share [r * ceil(N / world), (r + 1) * ceil(N / world)) on its device in the
-    classifier's batches; one all-reduce; every rank returns the same values."""
-    import torch
-    N = images.shape[0]
-    per = -(-N // world)
-    lo, hi = min(rank * per, N), min((rank + 1) * per, N)
+    """(mu, sigma, n) of pool_3 over `images` (features.pool3_batches: numpy or a `utils.data.DeviceDataset`).  Rank r
+    classifies its `features.share` of them on its device; one all-reduce; every rank returns the same values."""
     acc = MomentAccumulator(classifier.plan.pool3_channels, classifier.device)
-    bs = classifier.batch_size
-    for i in range(lo, hi, bs):
-        if hasattr(images, "rows"):
-            x = images.rows(i, min(i + bs, hi))
-        else:
-            x = torch.from_numpy(np.ascontiguousarray(images[i:min(i + bs, hi)], np.float32)).to(classifier.device)
-        acc.update(classifier.run(x, 127.5, 127.5)[0])
+    for rows in features.pool3_batches(classifier, images, *features.share(images.shape[0], rank, world)):
+        acc.update(rows)
     n, s, o = acc.all_reduce().moments()
     mu, sigma = stats_from_moments(n, s, o)
     return mu, sigma, n
+
+
+class FidMetric(features.HookMetric):
+    """real = (mu, sigma) of the real data.  pool_3 of exactly the eval_samples samples the score covers goes into fp64
+    moments on the device, one SUM all-reduce per evaluated model replaces a feature gather, rank 0 finalises on the host
+    and broadcasts the scalar."""
+    key, closing = "fid", 'min FID was %.4f, iter was %d'
+
+    def begin(self):
+        self.acc = MomentAccumulator(self.classifier.plan.pool3_channels, self.classifier.device)
+
+    def take(self, rows):
+        self.acc.update(rows)
+
+    def finish(self, tag, bank):
+        import torch
+        from .. import parallel
+        self.acc.all_reduce()
+        d = torch.zeros(1, dtype=torch.float64, device=self.classifier.device)
+        if self.rank == 0:
+            d[0] = frechet_distance(*stats_from_moments(*self.acc.moments()), self.real[0], self.real[1])
+            print('%sFID was %.4f' % (tag, float(d)))
+        d = float(parallel.broadcast_(d))
+        self.keep_minimum(d)
+        return d
 
 
 def main(argv=None):

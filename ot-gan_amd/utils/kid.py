@@ -25,6 +25,7 @@ subsets from different pools of rows.  Each is an unbiased estimate of the same 
 import numpy as np
 
 from .. import _lib
+from .features import FeatureBank, HookMetric, kernel_rows, real_bank, share    # (FeatureBank, real_bank: also this module's names)
 
 
 def subset_indices(n, m, count, seed, side, first=0, step=1):
@@ -50,10 +51,7 @@ def mmd2_from_sums(sums, m):
 def effective_subset_size(subset_size, eval_samples, real_samples, world=1):
     """The subset size KID can use: `subset_size`, cut to the smallest rank's surviving generated rows (the hook's `mine`)
     and to the smallest rank's share of the `real_samples` real rows.  Fewer than 2 is a ValueError."""
-    share = -(-int(eval_samples) // world)
-    gen = min(min(max(int(eval_samples) - r * share, 0), share) for r in range(world))
-    per = -(-int(real_samples) // world)
-    real = min(min((r + 1) * per, int(real_samples)) - min(r * per, int(real_samples)) for r in range(world))
+    gen, real = (min(hi - lo for lo, hi in (share(n, r, world) for r in range(world))) for n in (eval_samples, real_samples))
     m = min(int(subset_size), gen, real)
     if m < 2:
         raise ValueError("KID needs subsets of at least 2 rows: --kid_subset_size %d, %d generated rows and %d real rows on "
@@ -72,23 +70,11 @@ def _index_table(idx, rows, name):
     return t
 
 
-def _rows(x, name):
-    import torch
-    if not (torch.is_tensor(x) and x.is_cuda):
-        raise _lib.OtganError("kid_sums takes CUDA (MI355X) feature tensors; there is no CPU fallback")
-    if x.dim() != 2 or x.dtype != torch.float32 or x.shape[1] % 4 or x.shape[1] == 0:
-        raise ValueError("%s must be float32 [rows, C] with C a positive multiple of 4, got %s %s" % (name, x.dtype, tuple(x.shape)))
-    # the kernel reads 16-byte pieces of a row: a slice it cannot read that way is copied
-    if x.stride(1) != 1 or x.stride(0) < x.shape[1] or x.stride(0) % 4 or x.data_ptr() % 16:
-        x = x.contiguous()
-    return x
-
-
 def kid_sums(x, xi, y, yi):
     """fp64 CUDA [nsub, 3]: (s0, s1, s2) of every subset.  x, y: fp32 CUDA [rows, C] (a column slice of a wider buffer
     passes its row stride on); xi, yi: int32 [nsub, m] row numbers (numpy or torch), checked here on the host."""
     import torch
-    x, y = _rows(x, "x"), _rows(y, "y")
+    x, y = kernel_rows(x, "x", "kid_sums"), kernel_rows(y, "y", "kid_sums")
     if x.shape[1] != y.shape[1] or x.device != y.device:
         raise ValueError("x %s and y %s must have the same channels and device" % (tuple(x.shape), tuple(y.shape)))
     xi, yi = _index_table(xi, x.shape[0], "xi"), _index_table(yi, y.shape[0], "yi")
@@ -113,60 +99,6 @@ def kid_sums(x, xi, y, yi):
     return out
 
 
-class FeatureBank:
-    """A preallocated fp32 [rows, C] device buffer that `append` fills with pool_3 rows; it never leaves the device.
-    `total`: the rows of the same bank over all ranks (the bank itself holds this rank's)."""
-
-    def __init__(self, rows, C, device="cuda", total=None):
-        import torch
-        self.C, self.device = int(C), torch.device(device)
-        if self.device.type != "cuda":
-            raise _lib.OtganError("FeatureBank lives on a CUDA (MI355X) device; there is no CPU fallback")
-        self.buf = torch.empty(int(rows), self.C, dtype=torch.float32, device=self.device)
-        self.n = 0
-        self.total = int(rows) if total is None else int(total)
-
-    def append(self, x):
-        import torch
-        if not (torch.is_tensor(x) and x.is_cuda):
-            raise _lib.OtganError("FeatureBank.append takes CUDA (MI355X) tensors; there is no CPU fallback")
-        if x.dim() != 2 or x.shape[1] != self.C or x.dtype != torch.float32:
-            raise ValueError("features must be float32 [n, %d], got %s %s" % (self.C, x.dtype, tuple(x.shape)))
-        if self.n + x.shape[0] > self.buf.shape[0]:
-            raise ValueError("%d more rows do not fit a bank of %d holding %d" % (x.shape[0], self.buf.shape[0], self.n))
-        self.buf[self.n:self.n + x.shape[0]].copy_(x)
-        self.n += x.shape[0]
-        return self
-
-    def clear(self):
-        self.n = 0
-        return self
-
-    @property
-    def rows(self):
-        """the filled part, fp32 [n, C]"""
-        return self.buf[:self.n]
-
-
-def real_bank(classifier, images, n, rank=0, world=1):
-    """pool_3 of the first n of `images` -- numpy [N, H, W, 3] in [-1, 1] or a `utils.data.DeviceDataset`, read as
-    `fid.dataset_stats` reads them -- as a FeatureBank: rank r holds the contiguous share
-    [r * ceil(n / world), (r + 1) * ceil(n / world))."""
-    import torch
-    n = min(int(n), images.shape[0])
-    per = -(-n // world)
-    lo, hi = min(rank * per, n), min((rank + 1) * per, n)
-    bank = FeatureBank(hi - lo, classifier.plan.pool3_channels, classifier.device, total=n)
-    bs = classifier.batch_size
-    for i in range(lo, hi, bs):
-        if hasattr(images, "rows"):
-            x = images.rows(i, min(i + bs, hi))
-        else:
-            x = torch.from_numpy(np.ascontiguousarray(images[i:min(i + bs, hi)], np.float32)).to(classifier.device)
-        bank.append(classifier.run(x, 127.5, 127.5)[0])
-    return bank
-
-
 def kid_values(gen_bank, real_bank, subsets, m, seed, rank=0, world=1):
     """numpy fp64 [subsets]: MMD^2 of every subset, the same on every rank.  Subset b comes from rank b % world's own rows
     of both banks (one `kid_sums` launch per rank); one SUM all-reduce of the vector, each entry with one contributor."""
@@ -184,3 +116,21 @@ def kid(gen_bank, real_bank, subsets, m, seed, rank=0, world=1):
     """(mean, std) of the subsets' MMD^2 (population std, numpy.std); see the module text for the role of the ranks."""
     v = kid_values(gen_bank, real_bank, subsets, m, seed, rank, world)
     return float(np.mean(v)), float(np.std(v))
+
+
+class KidMetric(HookMetric):
+    """real = the real data's FeatureBank.  (mean, std) over the subsets of the bank the hook filled: one fused kernel-sum
+    launch per rank, one small all-reduce."""
+    key, uses_bank, closing = "kid", True, 'min KID was %.6f, iter was %d'
+
+    def __init__(self, *a):
+        super().__init__(*a)
+        if "kid_m" not in self.state:
+            self.state["kid_m"] = effective_subset_size(self.args.kid_subset_size, self.args.eval_samples, self.real.total, self.world)
+
+    def finish(self, tag, bank):
+        k = kid(bank, self.real, self.args.kid_subsets, self.state["kid_m"], getattr(self.args, "seed", 1), self.rank, self.world)
+        if self.rank == 0:
+            print('%sKID was %.6f, std was %.6f' % (tag, k[0], k[1]))
+        self.keep_minimum(k[0])
+        return k

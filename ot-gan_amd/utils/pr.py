@@ -23,6 +23,7 @@ in whichever call, tile or operand role it is computed, a K-th smallest value an
 the columns -- so, UNLIKE KID, two ranks return exactly the values one process returns.
 """
 from .. import _lib
+from .features import HookMetric, gather_rows, kernel_rows    # (gather_rows: also this module's name)
 
 MAX_K = 8
 
@@ -39,25 +40,13 @@ def check_neighbours(k, gen_rows, real_rows):
     return k
 
 
-def _rows(x, name):
-    import torch
-    if not (torch.is_tensor(x) and x.is_cuda):
-        raise _lib.OtganError("knn takes CUDA (MI355X) feature tensors; there is no CPU fallback")
-    if x.dim() != 2 or x.dtype != torch.float32 or x.shape[1] % 4 or x.shape[1] == 0:
-        raise ValueError("%s must be float32 [rows, C] with C a positive multiple of 4, got %s %s" % (name, x.dtype, tuple(x.shape)))
-    # the kernel reads 16-byte pieces of a row: a slice it cannot read that way is copied
-    if x.stride(1) != 1 or x.stride(0) < x.shape[1] or x.stride(0) % 4 or x.data_ptr() % 16:
-        x = x.contiguous()
-    return x
-
-
 def knn(q, y, k, self0=-1, thresh=None):
     """(nearest fp64 CUDA [nq, k], inside int32 CUDA [nq] or None): per row of q the k smallest d2 to the rows of y,
     ascending (+inf where fewer were counted), and -- with thresh, fp64 [ny] -- the number of columns j with
     d2 <= thresh[j].  Column self0 + i is skipped for row i (self0 = -1: none).  q, y: fp32 CUDA [rows, C] (a column
     slice of a wider buffer passes its row stride on)."""
     import torch
-    q, y = _rows(q, "q"), _rows(y, "y")
+    q, y = kernel_rows(q, "q", "knn"), kernel_rows(y, "y", "knn")
     if q.shape[1] != y.shape[1] or q.device != y.device:
         raise ValueError("q %s and y %s must have the same channels and device" % (tuple(q.shape), tuple(y.shape)))
     k, self0 = int(k), int(self0)
@@ -81,23 +70,6 @@ def knn(q, y, k, self0=-1, thresh=None):
                                    nearest.data_ptr() if k else None, inside.data_ptr() if inside is not None else None,
                                    ws.data_ptr(), nbytes, _lib.stream_ptr()), "knn")
     return nearest, inside
-
-
-def gather_rows(x, rank=0, world=1):
-    """(all ranks' rows of x in rank order, this rank's first row among them).  The shares may differ: each is padded
-    to the largest for the one all-gather and cut again."""
-    import torch
-    from .. import parallel
-    if world == 1:
-        return x, 0
-    counts = parallel.all_gather_rows(torch.tensor([x.shape[0]], dtype=torch.int64, device=x.device)).tolist()
-    big = max(counts)
-    if x.shape[0] < big:
-        x = torch.cat([x, x.new_zeros((big - x.shape[0],) + tuple(x.shape[1:]))])
-    allx = parallel.all_gather_rows(x)
-    if min(counts) < big:
-        allx = torch.cat([allx[r * big:r * big + n] for r, n in enumerate(counts)])
-    return allx, sum(counts[:rank])
 
 
 def radii(bank_rows, k, rank=0, world=1, gathered=None):
@@ -143,3 +115,15 @@ def precision_recall(gen_bank, real_bank, k, real_radii=None, rank=0, world=1):
     every world size.  `real_radii`: radii(real_bank.rows, k, rank, world), computed once per run."""
     check_neighbours(k, gen_bank.total, real_bank.total)
     return values_from_counts(counts(gen_bank, real_bank, k, real_radii, rank, world).tolist(), k)
+
+
+class PrMetric(HookMetric):
+    """real = the real data's FeatureBank, its radii in state["pr_real_radii"].  The four values of the bank the hook
+    filled: three fused k-NN passes, the same values for every world size."""
+    key, uses_bank = "pr", True
+
+    def finish(self, tag, bank):
+        v = precision_recall(bank, self.real, self.args.pr_neighbours, self.state["pr_real_radii"], self.rank, self.world)
+        if self.rank == 0:
+            print('%sprecision was %.4f, recall was %.4f, density was %.4f, coverage was %.4f' % ((tag,) + v))
+        return v

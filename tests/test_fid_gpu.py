@@ -12,24 +12,20 @@ cases, column sums exact; device against host moments 2.1e-13; the hook against 
 (d^2 = 0.589626047 against 0.589626082); 50 of 96 rows 1.5e-11; two ranks against one process 9.6e-14 (96 samples) and
 9.9e-13 (95).
 """
-import ctypes
-import functools
 import os
-import socket
-import tempfile
 from types import SimpleNamespace
 
 import numpy as np
 import pytest
 import torch
 
-import inception_graphs as G
+import metric_harness as H
+from metric_harness import DEV, EVALS, Replay as _Replay, interpreter as _interpreter, net as _net, pool3 as _pool3, sets as _sets
 from otgan_amd import _lib
-from otgan_amd.utils import fid, inception_net, tfgraph
+from otgan_amd.utils import fid
 from otgan_amd.utils.inception import inception_score_from_probs
 
 pytestmark = pytest.mark.gpu
-DEV = torch.device("cuda:0")
 TOL_KERNEL = 1e-12
 TOL_MOMENTS = 1e-9
 TOL_NET = 1e-5
@@ -120,40 +116,9 @@ def test_moments_kernel_rejects_bad_arguments():
 
 
 # ---------------------------------------------------------------- end to end on the narrow graph (C = 40)
-@functools.lru_cache(maxsize=None)
-def _graph():
-    nodes, data = G.narrow_graph()
-    return nodes, data, inception_net.lower(tfgraph.parse_graph(data))
-
-
-@functools.lru_cache(maxsize=None)
-def _sets():
-    """Set A and set B as generator output in [-1, 1] (fp32), the form the hook and `trainx` have."""
-    a = G.images(96, seed=1)
-    b = G.images(96, seed=2)
-    b = np.clip(0.5 * b + 0.25 * np.roll(b, 1, axis=2) + 40, 0, 255)
-    return tuple((im / 127.5 - 1.0).astype(np.float32) for im in (a, b))
-
-
-@functools.lru_cache(maxsize=None)
-def _interpreter(which):
-    """fp64 (pool_3, probabilities) of the images the device network sees for set `which`: 127.5 (x + 1)."""
-    x = _sets()[which].astype(np.float64)
-    p3, _, pr = G.reference_outputs(_graph()[0], 127.5 * (x + 1.0))
-    return p3, pr
-
-
 def _host_stats(p3):
     p3 = np.asarray(p3, np.float64)
     return np.mean(p3, 0), np.cov(p3, rowvar=False)
-
-
-def _net():
-    return inception_net.InceptionNet(_graph()[2], DEV)
-
-
-def _pool3(net, x):
-    return net.run(torch.as_tensor(x, device=DEV), 127.5, 127.5)[0]
 
 
 def _device_stats(p3):
@@ -165,37 +130,8 @@ def _device_stats(p3):
     return fid.stats_from_moments(n, s, o)
 
 
-class _DeviceOnly(torch.Tensor):
-    """A sample tensor that must stay on the device: reading it on the host fails."""
-    def cpu(self, *a, **k):
-        raise AssertionError("a generated sample reached the host")
-
-    def numpy(self, *a, **k):
-        raise AssertionError("a generated sample reached the host")
-
-    def __array__(self, *a, **k):
-        raise AssertionError("a generated sample reached the host")
-
-    def tolist(self):
-        raise AssertionError("a generated sample reached the host")
-
-
-class _Replay:
-    """A model whose generator (and EMA generator) replays the rows of x in the batches the hook asks for."""
-    def __init__(self, x):
-        self.device = DEV
-        self.x = torch.as_tensor(x, device=DEV)
-        self.at = {False: 0, True: 0}
-
-    def sample(self, n, ema=False):
-        i = self.at[ema]
-        assert i + n <= self.x.shape[0], "the hook drew more samples than its share"
-        self.at[ema] = i + n
-        return self.x[i:i + n].clone().as_subclass(_DeviceOnly)
-
-
 def _state(real):
-    return {"max": 0.0, "iter": 0, "epoch": 3, "fid_real": real}
+    return H.state(fid_real=real)
 
 
 def test_device_moments_against_host_moments_of_the_same_pool3():
@@ -255,23 +191,8 @@ def test_hook_covers_exactly_eval_samples_rows():
     assert abs(full - ref) > 1e-3 * ref                      # (the other 46 rows would have shown)
 
 
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    p = s.getsockname()[1]
-    s.close()
-    return p
-
-
-EVALS = (96, 95)        # 95: the ranks draw 48 each and the last row of rank 1 falls to the truncation
-
-
-def _rank_worker(rank, world, port, path):
-    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world), LOCAL_RANK="0")
-    from otgan_amd import parallel
+def _rank_worker(rank, world, path):
     from otgan_amd.train import inception_hook
-    parallel.init_from_env(backend="gloo")
-    torch.cuda.set_device(0)
     net = _net()
     mu, sigma, _ = fid.load_stats(path + "real.npz", net.plan.pool3_channels)
     xa = _sets()[0]
@@ -281,29 +202,15 @@ def _rank_worker(rank, world, port, path):
         out = inception_hook(_Replay(xa[rank * share:(rank + 1) * share]), SimpleNamespace(eval_samples=ev), net,
                              _state((mu, sigma)), rank, world)
         res[ev] = (out["fid_live"], out["fid_EMA"], out["live"][0])
-    torch.save(res, path + str(rank))
-    parallel.barrier()
-    torch.distributed.destroy_process_group()
+    return res
 
 
 def test_two_ranks_equal_one_process():
-    import torch.multiprocessing as mp
     from otgan_amd.train import inception_hook
     net = _net()
     xa, xb = _sets()
     mu, sigma, n = fid.dataset_stats(net, xb)
-    with tempfile.TemporaryDirectory() as td:
-        path = os.path.join(td, "r")
-        fid.save_stats(path + "real.npz", mu, sigma, n)
-        port = _free_port()
-        ctx = mp.get_context("spawn")
-        procs = [ctx.Process(target=_rank_worker, args=(r, 2, port, path)) for r in range(2)]
-        for p in procs:
-            p.start()
-        for p in procs:
-            p.join(600)
-            assert p.exitcode == 0
-        got = [torch.load(path + str(r)) for r in range(2)]
+    got = H.two_ranks(_rank_worker, lambda path: fid.save_stats(path + "real.npz", mu, sigma, n))
     for ev in EVALS:
         one = inception_hook(_Replay(xa), SimpleNamespace(eval_samples=ev), net, _state((mu, sigma)))
         assert got[0][ev] == got[1][ev], (ev, got)           # every rank ends with the same values
@@ -317,13 +224,8 @@ def test_two_ranks_equal_one_process():
 
 def test_train_main_with_fid_stats(tmp_path, capsys):
     from otgan_amd import train
-    graph = tmp_path / tfgraph.GRAPH_FILE
-    graph.write_bytes(_graph()[1])
     stats = str(tmp_path / "real_stats.npz")
-    common = ["--synthetic", "--synthetic_size", "48", "--nr_gpu", "2", "--batch_size", "8", "--nr_sinkhorn_iter", "10",
-              "--sinkhorn_lambda", "100", "--nr_gen_per_disc", "2", "--save_dir", str(tmp_path / "run"), "--seed", "3",
-              "--max_steps", "6", "--eval_every", "1", "--eval_samples", "20", "--inception_model", str(graph)]
-    # 3 steps per epoch: epochs 0 and 1; the hook runs after epoch 1 (train.py:245 skips the first epoch of a run)
+    common = H.train_args(tmp_path)
     train.main(common + ["--fid_stats", stats, "--fid_real_samples", "40"])
     out = capsys.readouterr().out
     assert "computed from 40 training images" in out and stats in out

@@ -15,27 +15,23 @@ Measured on an MI355X, error / bar: kernel 2.7e-6 (2 x 1000 x 2048), 2.6e-4 (3 x
 2.9e-3; the hook against the fp64 interpreter 8.5e-5 on the worst subset and 3.4e-5 on the mean (KID 0.060870, bar
 5.4e-5); 50 of 96 rows 1.0e-8 of the device bar; two ranks 1.0e-8 (96 samples) and 3.1e-8 (95).
 """
-import functools
-import os
-import socket
-import tempfile
 from types import SimpleNamespace
 
 import numpy as np
 import pytest
 import torch
 
-import inception_graphs as G
 import kid_ref
+import metric_harness as H
+from metric_harness import (DEV, EVALS, SEED, Replay as _Replay, interpreter as _interpreter, kinds as _kinds, net as _net,
+                            pool3 as _pool3, sets as _sets, train_args as _common)
 from otgan_amd import _lib
-from otgan_amd.utils import inception_net, kid, tfgraph
+from otgan_amd.utils import kid
 from otgan_amd.utils.inception import inception_score_from_probs
 
 pytestmark = pytest.mark.gpu
-DEV = torch.device("cuda:0")
 TOL_NET = 1e-5
 TOL_DEVICE = 1e-9
-SEED = 5
 
 
 # ---------------------------------------------------------------- the kernel
@@ -241,72 +237,12 @@ def test_feature_bank():
 
 
 # ---------------------------------------------------------------- end to end on the narrow graph (C = 40)
-@functools.lru_cache(maxsize=None)
-def _graph():
-    nodes, data = G.narrow_graph()
-    return nodes, data, inception_net.lower(tfgraph.parse_graph(data))
-
-
-@functools.lru_cache(maxsize=None)
-def _sets():
-    """Set A and set B as generator output in [-1, 1] (fp32): the sets of tests/test_fid_gpu.py, restated."""
-    a = G.images(96, seed=1)
-    b = G.images(96, seed=2)
-    b = np.clip(0.5 * b + 0.25 * np.roll(b, 1, axis=2) + 40, 0, 255)
-    return tuple((im / 127.5 - 1.0).astype(np.float32) for im in (a, b))
-
-
-@functools.lru_cache(maxsize=None)
-def _interpreter(which):
-    """fp64 (pool_3, probabilities) of the images the device network sees for set `which`: 127.5 (x + 1)."""
-    x = _sets()[which].astype(np.float64)
-    p3, _, pr = G.reference_outputs(_graph()[0], 127.5 * (x + 1.0))
-    return p3, pr
-
-
-def _net():
-    return inception_net.InceptionNet(_graph()[2], DEV)
-
-
-def _pool3(net, x):
-    return net.run(torch.as_tensor(x, device=DEV), 127.5, 127.5)[0]
-
-
-class _DeviceOnly(torch.Tensor):
-    """A sample tensor that must stay on the device: reading it on the host fails."""
-    def cpu(self, *a, **k):
-        raise AssertionError("a generated sample reached the host")
-
-    def numpy(self, *a, **k):
-        raise AssertionError("a generated sample reached the host")
-
-    def __array__(self, *a, **k):
-        raise AssertionError("a generated sample reached the host")
-
-    def tolist(self):
-        raise AssertionError("a generated sample reached the host")
-
-
-class _Replay:
-    """A model whose generator (and EMA generator) replays the rows of x in the batches the hook asks for."""
-    def __init__(self, x):
-        self.device = DEV
-        self.x = torch.as_tensor(x, device=DEV)
-        self.at = {False: 0, True: 0}
-
-    def sample(self, n, ema=False):
-        i = self.at[ema]
-        assert i + n <= self.x.shape[0], "the hook drew more samples than its share"
-        self.at[ema] = i + n
-        return self.x[i:i + n].clone().as_subclass(_DeviceOnly)
-
-
 def _args(eval_samples, subsets=8, size=32):
     return SimpleNamespace(eval_samples=eval_samples, kid_subsets=subsets, kid_subset_size=size, seed=SEED)
 
 
 def _state(real):
-    return {"max": 0.0, "iter": 0, "epoch": 3, "kid_real": real}
+    return H.state(kid_real=real)
 
 
 def test_hook_against_the_fp64_interpreter(capsys):
@@ -377,23 +313,8 @@ def test_hook_covers_exactly_eval_samples_rows():
     assert abs(full.mean() - ref.mean()) > 1e4 * TOL_DEVICE * scale.mean()  # (the other 46 rows would have shown)
 
 
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    p = s.getsockname()[1]
-    s.close()
-    return p
-
-
-EVALS = (96, 95)        # 95: the ranks draw 48 each and the last row of rank 1 falls to the truncation
-
-
-def _rank_worker(rank, world, port, path):
-    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world), LOCAL_RANK="0")
-    from otgan_amd import parallel
+def _rank_worker(rank, world, path):
     from otgan_amd.train import inception_hook
-    parallel.init_from_env(backend="gloo")
-    torch.cuda.set_device(0)
     net = _net()
     xa, xb = _sets()
     real = kid.real_bank(net, xb, 96, rank, world)
@@ -403,27 +324,14 @@ def _rank_worker(rank, world, port, path):
         share = -(-ev // world)
         out = inception_hook(_Replay(xa[rank * share:(rank + 1) * share]), _args(ev), net, _state(real), rank, world)
         res[ev] = (out["kid_live"], out["kid_EMA"], out["live"][0])
-    torch.save(res, path + str(rank))
-    parallel.barrier()
-    torch.distributed.destroy_process_group()
+    return res
 
 
 def test_two_ranks_follow_the_documented_rule():
     """Subset b comes from rank b % 2's own rows of both banks; both ranks end with the same (mean, std)."""
-    import torch.multiprocessing as mp
     net = _net()
     xa, xb = _sets()
-    with tempfile.TemporaryDirectory() as td:
-        path = os.path.join(td, "r")
-        port = _free_port()
-        ctx = mp.get_context("spawn")
-        procs = [ctx.Process(target=_rank_worker, args=(r, 2, port, path)) for r in range(2)]
-        for p in procs:
-            p.start()
-        for p in procs:
-            p.join(600)
-            assert p.exitcode == 0
-        got = [torch.load(path + str(r)) for r in range(2)]
+    got = H.two_ranks(_rank_worker)
     pa, pb = _pool3(net, xa).cpu().numpy(), _pool3(net, xb).cpu().numpy()
     for ev in EVALS:
         assert got[0][ev] == got[1][ev], (ev, got)           # every rank ends with the same values
@@ -443,22 +351,9 @@ def test_two_ranks_follow_the_documented_rule():
             assert abs(std - ref.std()) <= TOL_DEVICE * scale.max()
 
 
-def _common(tmp_path):
-    graph = tmp_path / tfgraph.GRAPH_FILE
-    graph.write_bytes(_graph()[1])
-    return ["--synthetic", "--synthetic_size", "48", "--nr_gpu", "2", "--batch_size", "8", "--nr_sinkhorn_iter", "10",
-            "--sinkhorn_lambda", "100", "--nr_gen_per_disc", "2", "--save_dir", str(tmp_path / "run"), "--seed", "3",
-            "--max_steps", "6", "--eval_every", "1", "--eval_samples", "20", "--inception_model", str(graph)]
-
-
-def _kinds(lines, names):
-    return [k for l in lines for k in names if l.startswith(k)]
-
-
 def test_train_main_with_kid(tmp_path, capsys):
     from otgan_amd import train
     common = _common(tmp_path)
-    # 3 steps per epoch: epochs 0 and 1; the hook runs after epoch 1 (train.py:245 skips the first epoch of a run)
     train.main(common + ["--kid_subsets", "4", "--kid_subset_size", "8"])
     out = capsys.readouterr().out
     assert "KID features of the real data: pool_3 of the first 20 training images" in out and "KID subsets hold" not in out

@@ -17,8 +17,6 @@ graph (0.1771, 0.9583, 0.0972, 0.1771), the fp64 interpreter's values exactly, w
 two ranks and one process (0.1771, 0.9579, 0.0972, 0.1789) on 96 x 95 rows and (0.1789, 0.9579, 0.0982, 0.1789) on 95 x 95.
 """
 import functools
-import os
-import tempfile
 from types import SimpleNamespace
 
 import numpy as np
@@ -26,12 +24,12 @@ import pytest
 import torch
 
 import pr_ref
-import test_kid_gpu as kid_tests          # the narrow graph, the two 96-image sets, the replaying model, the rank plumbing
+import metric_harness as H
+from metric_harness import DEV, EVALS    # (96, and 95: the last row of rank 1 falls to the truncation, the shares differ)
 from otgan_amd import _lib
 from otgan_amd.utils import fid, kid, pr
 
 pytestmark = pytest.mark.gpu
-DEV = torch.device("cuda:0")
 TOL_NET = 1e-5
 MARGIN = 1000.0
 K = 3
@@ -321,28 +319,28 @@ def test_wrapper_rejects_bad_inputs_on_the_host():
 
 # ---------------------------------------------------------------- the hook on the narrow graph (C = 40)
 def _args(eval_samples, k=K, **more):
-    return SimpleNamespace(eval_samples=eval_samples, pr_neighbours=k, seed=kid_tests.SEED, **more)
+    return SimpleNamespace(eval_samples=eval_samples, pr_neighbours=k, seed=H.SEED, **more)
 
 
 def _state(real, k=K):
-    return {"max": 0.0, "iter": 0, "epoch": 3, "pr_real": real, "pr_real_radii": pr.radii(real.rows, k)}
+    return H.state(pr_real=real, pr_real_radii=pr.radii(real.rows, k))
 
 
 @functools.lru_cache(maxsize=None)
 def _device_rows():
     """pool_3 of the two 96-image sets from the device network (numpy): what the hook's banks hold."""
-    net = kid_tests._net()
-    xa, xb = kid_tests._sets()
-    return kid_tests._pool3(net, xa).cpu().numpy(), kid_tests._pool3(net, xb).cpu().numpy()
+    net = H.net()
+    xa, xb = H.sets()
+    return H.pool3(net, xa).cpu().numpy(), H.pool3(net, xb).cpu().numpy()
 
 
 def test_hook_equals_the_reference_on_the_device_features(capsys):
     from otgan_amd.train import inception_hook
-    net = kid_tests._net()
-    xa, xb = kid_tests._sets()
+    net = H.net()
+    xa, xb = H.sets()
     real = kid.real_bank(net, xb, 96)
     state = _state(real)
-    model = kid_tests._Replay(xa)                        # its samples fail when read on the host
+    model = H.Replay(xa)                        # its samples fail when read on the host
     out = inception_hook(model, _args(96), net, state)
     printed = capsys.readouterr().out
     # the rows the banks hold are the network's pool_3 of the two sets (the batches differ: not bit for bit) ...
@@ -365,7 +363,7 @@ def test_hook_equals_the_reference_on_the_device_features(capsys):
 
     # 50 of the 96 samples: exactly those rows
     state50 = _state(real)
-    out50 = inception_hook(kid_tests._Replay(xa), _args(50), net, state50)
+    out50 = inception_hook(H.Replay(xa), _args(50), net, state50)
     capsys.readouterr()
     pa50 = state50["kid_gen"].rows.cpu().numpy()
     assert pa50.shape == (50, 40) and np.allclose(pa50, _device_rows()[0][:50], rtol=1e-5, atol=1e-6)
@@ -376,34 +374,35 @@ def test_hook_equals_the_reference_on_the_device_features(capsys):
 
 def test_hook_prints_after_the_fid_and_kid_lines(capsys):
     from otgan_amd.train import inception_hook
-    net = kid_tests._net()
-    xa, xb = kid_tests._sets()
+    net = H.net()
+    xa, xb = H.sets()
     real = kid.real_bank(net, xb, 96)
     mu, sigma, _ = fid.dataset_stats(net, xb)
     state = _state(real)
     state.update(fid_real=(mu, sigma), kid_real=real)    # KID and P&R share the real bank
-    out = inception_hook(kid_tests._Replay(xa), _args(96, kid_subsets=8, kid_subset_size=32), net, state)
+    out = inception_hook(H.Replay(xa), _args(96, kid_subsets=8, kid_subset_size=32), net, state)
     lines = capsys.readouterr().out.splitlines()
     names = ("inception score was", "FID was", "KID was", "precision was", "EMA inception score was", "EMA FID was",
              "EMA KID was", "EMA precision was", "max inception score was", "min FID was", "min KID was")
     assert [l.split(",")[0].rsplit(" ", 1)[0] for l in lines] == [n for n in names], lines
-    alone = inception_hook(kid_tests._Replay(xa), _args(96), net, _state(real))
+    alone = inception_hook(H.Replay(xa), _args(96), net, _state(real))
     capsys.readouterr()
     assert out["pr_live"] == alone["pr_live"] and out["live"] == alone["live"]
-    kid_only = inception_hook(kid_tests._Replay(xa), kid_tests._args(96), net, kid_tests._state(real))
+    kid_only = inception_hook(H.Replay(xa), SimpleNamespace(eval_samples=96, kid_subsets=8, kid_subset_size=32, seed=H.SEED),
+                              net, H.state(kid_real=real))
     capsys.readouterr()
     assert out["kid_live"] == kid_only["kid_live"]       # KID is what it is without --pr_neighbours
 
 
 def test_hook_with_zero_neighbours_is_the_hook_without_the_flag(capsys):
     from otgan_amd.train import inception_hook
-    net = kid_tests._net()
-    xa, xb = kid_tests._sets()
+    net = H.net()
+    xa, xb = H.sets()
     real = kid.real_bank(net, xb, 96)
     state0, state1 = _state(real), {"max": 0.0, "iter": 0, "epoch": 3}
-    out0 = inception_hook(kid_tests._Replay(xa), _args(96, k=0), net, state0)
+    out0 = inception_hook(H.Replay(xa), _args(96, k=0), net, state0)
     printed0 = capsys.readouterr().out
-    out1 = inception_hook(kid_tests._Replay(xa), SimpleNamespace(eval_samples=96), net, state1)
+    out1 = inception_hook(H.Replay(xa), SimpleNamespace(eval_samples=96), net, state1)
     printed1 = capsys.readouterr().out
     assert set(out0) == {"live", "EMA"} and out0 == out1
     assert printed0 == printed1 and "precision" not in printed0
@@ -418,9 +417,9 @@ def _uncertain(d, thresh, tol):
 
 def test_hook_against_the_fp64_interpreter(capsys):
     from otgan_amd.train import inception_hook
-    net = kid_tests._net()
-    xa, xb = kid_tests._sets()
-    (p3a, _), (p3b, _) = kid_tests._interpreter(0), kid_tests._interpreter(1)
+    net = H.net()
+    xa, xb = H.sets()
+    (p3a, _), (p3b, _) = H.interpreter(0), H.interpreter(1)
     ref = pr_ref.values(p3a, p3b, K)
     d = pr_ref.dist2(p3a, p3b)
     na, nb = np.sqrt((p3a * p3a).sum(axis=1)), np.sqrt((p3b * p3b).sum(axis=1))
@@ -430,7 +429,7 @@ def test_hook_against_the_fp64_interpreter(capsys):
     # a generated row takes part in precision and density through the real balls; a real row in recall through the
     # generated balls and in coverage through its own ball
     ug, ur = int(in_real.any(axis=1).sum()), int((in_gen.any(axis=0) | in_real.any(axis=0)).sum())
-    out = inception_hook(kid_tests._Replay(xa), _args(96), net, _state(kid.real_bank(net, xb, 96)))
+    out = inception_hook(H.Replay(xa), _args(96), net, _state(kid.real_bank(net, xb, 96)))
     capsys.readouterr()
     got = out["pr_live"]
     bars = (ug / 96, ur / 96, min(ug / 96, int(in_real.sum()) / (K * 96)), ur / 96)
@@ -445,17 +444,10 @@ def test_hook_against_the_fp64_interpreter(capsys):
 
 
 # ---------------------------------------------------------------- two ranks equal one process
-EVALS = kid_tests.EVALS         # 96, and 95: the last row of rank 1 falls to the truncation, the shares differ
-
-
-def _rank_worker(rank, world, port, path):
-    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world), LOCAL_RANK="0")
-    from otgan_amd import parallel
+def _rank_worker(rank, world, path):
     from otgan_amd.train import inception_hook
-    parallel.init_from_env(backend="gloo")
-    torch.cuda.set_device(0)
-    net = kid_tests._net()
-    xa, xb = kid_tests._sets()
+    net = H.net()
+    xa, xb = H.sets()
     real = kid.real_bank(net, xb, 95, rank, world)               # shares of 48 and 47 rows
     assert real.n == 48 - rank and real.total == 95
     radii = pr.radii(real.rows, K, rank, world)
@@ -463,27 +455,14 @@ def _rank_worker(rank, world, port, path):
     res = {"real": real.rows.cpu(), "radii": radii.cpu()}
     for ev in EVALS:
         share = -(-ev // world)
-        state = {"max": 0.0, "iter": 0, "epoch": 3, "pr_real": real, "pr_real_radii": radii}
-        out = inception_hook(kid_tests._Replay(xa[rank * share:(rank + 1) * share]), _args(ev), net, state, rank, world)
+        state = H.state(pr_real=real, pr_real_radii=radii)
+        out = inception_hook(H.Replay(xa[rank * share:(rank + 1) * share]), _args(ev), net, state, rank, world)
         res[ev] = (out["pr_live"], out["pr_EMA"], state["kid_gen"].rows.cpu())
-    torch.save(res, path + str(rank))
-    parallel.barrier()
-    torch.distributed.destroy_process_group()
+    return res
 
 
 def test_two_ranks_return_exactly_what_one_process_returns():
-    import torch.multiprocessing as mp
-    with tempfile.TemporaryDirectory() as td:
-        path = os.path.join(td, "r")
-        port = kid_tests._free_port()
-        ctx = mp.get_context("spawn")
-        procs = [ctx.Process(target=_rank_worker, args=(r, 2, port, path)) for r in range(2)]
-        for p in procs:
-            p.start()
-        for p in procs:
-            p.join(600)
-            assert p.exitcode == 0
-        got = [torch.load(path + str(r)) for r in range(2)]
+    got = H.two_ranks(_rank_worker)
     real = torch.cat([got[0]["real"], got[1]["real"]])
     assert real.shape[0] == 95 and torch.equal(got[0]["radii"], got[1]["radii"])
     rb = _bank(real)
@@ -502,7 +481,7 @@ def test_two_ranks_return_exactly_what_one_process_returns():
 # ---------------------------------------------------------------- train.main end to end
 def test_train_main_with_precision_and_recall(tmp_path, capsys):
     from otgan_amd import train
-    common = kid_tests._common(tmp_path)
+    common = H.train_args(tmp_path)
     train.main(common + ["--pr_neighbours", "3"])
     out = capsys.readouterr().out
     assert out.count("precision / recall features of the real data: pool_3 of the first 20 training images, kept on the device") == 1
@@ -517,7 +496,7 @@ def test_train_main_with_precision_and_recall(tmp_path, capsys):
     train.main(common + ["--pr_neighbours", "3", "--kid_subsets", "4", "--kid_subset_size", "8"])
     out = capsys.readouterr().out
     assert "the bank KID keeps" in out
-    kinds = kid_tests._kinds(out.splitlines(), ("inception score was", "KID was", "precision was", "EMA inception score was",
+    kinds = H.kinds(out.splitlines(), ("inception score was", "KID was", "precision was", "EMA inception score was",
                                                 "EMA KID was", "EMA precision was", "max inception score was", "min KID was"))
     assert kinds == ["inception score was", "KID was", "precision was", "EMA inception score was", "EMA KID was",
                      "EMA precision was", "max inception score was", "min KID was"], out
@@ -529,7 +508,7 @@ def test_train_main_with_precision_and_recall(tmp_path, capsys):
 
 def test_train_main_precision_and_recall_notices(tmp_path, capsys):
     from otgan_amd import train
-    common = kid_tests._common(tmp_path)
+    common = H.train_args(tmp_path)
     # more neighbours than the 20 samples have rows: an error before the first step
     with pytest.raises(ValueError):
         train.main(common + ["--pr_neighbours", "30"])
