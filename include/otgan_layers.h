@@ -260,6 +260,12 @@ int otgan_dense16_bwd_slice_f32(int N, int H, int W, int npairs, const float* g,
                                 float* amax_out, void* stream);
 int otgan_conv2d_prepare_filters_f32(const otgan_conv_desc* d, int which, const float* w, void* filters,
                                      size_t filter_bytes, void* stream);
+/* The same filters from the RAW weight-norm direction V[KH*KW][Cin_eff][Cout] (HWIO) and scale[Cout] = g * inv_norm
+ * (otgan_weightnorm_scale_amax_f32), bit-identical to the ones otgan_conv2d_prepare_filters_f32 makes from the normalised
+ * w / wT -- which a caller on this route never writes.  Same `which` values, same refusals by the same codes; it needs
+ * otgan_conv_desc::w_amax, and which = 0 / 1 of a FOLDED layer (filters from the folded weights) is OTGAN_ERR_UNSUPPORTED. */
+int otgan_conv2d_prepare_filters_raw_f32(const otgan_conv_desc* d, int which, const float* V, const float* scale,
+                                         void* filters, size_t filter_bytes, void* stream);
 int otgan_conv2d_fwd_pf_f32(const otgan_conv_desc* d, const float* x, const int32_t* cmap,
                             const float* wT, const void* filters, const float* bias, float* y,
                             void* workspace, size_t workspace_bytes, void* stream);
@@ -280,6 +286,13 @@ int otgan_weightnorm_fwd_f32(const float* V, const float* g, int K, int Cout, fl
  * otgan_conv_desc::w_amax to otgan_conv2d_prepare_filters_f32 */
 int otgan_weightnorm_fwd_amax_f32(const float* V, const float* g, int K, int Cout, float* w, float* wT,
                                   float* inv_norm, float* w_amax, void* stream);
+/* What otgan_weightnorm_fwd_amax_f32 leaves beside w, without writing w: inv_norm (bit-identical: same reduction), scale[c] =
+ * g[c] * inv_norm[c] (the factor w = V * scale is rounded with) and the amax record of that never-materialised w, from ONE
+ * pass over V (column sums of squares and column maxima of |V|) and a finish launch.  w_amax: zeroed by the caller;
+ * scratch: otgan_weightnorm_scale_scratch_floats(K, Cout) floats, 16-byte aligned. */
+size_t otgan_weightnorm_scale_scratch_floats(int K, int Cout);
+int otgan_weightnorm_scale_amax_f32(const float* V, const float* g, int K, int Cout, float* inv_norm, float* scale,
+                                    float* w_amax, float* scratch, size_t scratch_floats, void* stream);
 /* dV, dg from dw (scratch: Cout floats). */
 int otgan_weightnorm_bwd_f32(const float* V, const float* g, const float* inv_norm,
                              const float* dw, int K, int Cout, float* dV, float* dg,

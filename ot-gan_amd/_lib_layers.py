@@ -88,6 +88,9 @@ SIGNATURES = {
                                           c_size_t, c_fp]),
     "otgan_weightnorm_fwd_f32": (c_int, [c_fp, c_fp, c_int, c_int, c_fp, c_fp, c_fp, c_fp]),
     "otgan_weightnorm_fwd_amax_f32": (c_int, [c_fp, c_fp, c_int, c_int, c_fp, c_fp, c_fp, c_fp, c_fp]),
+    "otgan_weightnorm_scale_scratch_floats": (c_size_t, [c_int, c_int]),
+    "otgan_weightnorm_scale_amax_f32": (c_int, [c_fp, c_fp, c_int, c_int, c_fp, c_fp, c_fp, c_fp, c_size_t, c_fp]),
+    "otgan_conv2d_prepare_filters_raw_f32": (c_int, [P_DESC, c_int, c_fp, c_fp, c_fp, c_size_t, c_fp]),
     "otgan_weightnorm_bwd_f32": (c_int, [c_fp, c_fp, c_fp, c_fp, c_int, c_int, c_fp, c_fp, c_fp, c_fp]),
     "otgan_weightnorm_fwd_batched16_f32": (c_int, [ctypes.POINTER(WnFwdLayer), c_int, c_fp]),
     "otgan_weightnorm_bwd_batched16_f32": (c_int, [ctypes.POINTER(WnBwdLayer), c_int, c_fp]),

@@ -3057,6 +3057,41 @@ int otgan_conv2d_prepare_filters_f32(const otgan_conv_desc* d, int which, const 
   return rc;
 }
 
+int otgan_conv2d_prepare_filters_raw_f32(const otgan_conv_desc* d, int which, const float* V, const float* scale,
+                                         void* filters, size_t filter_bytes, void* stream) {
+  Geo g;
+  int rc = make_geo(d, &g);
+  if (rc) return rc;
+  const size_t need = otgan_conv2d_filter_bytes(d, which);
+  OTGAN_CHECK_ARG(need > 0, "this layer / pass has no Winograd-domain filters");
+  OTGAN_CHECK_ARG(V && scale && filters && aligned16(V) && aligned16(scale) && aligned16(filters), "null or misaligned pointer");
+  OTGAN_CHECK_ARG(d->w_amax, "filters from the raw weights need the amax record of the normalised weights (w_amax)");
+  if (filter_bytes < need) {
+    otgan_set_error("conv2d filter buffer too small: need %zu, got %zu", need, filter_bytes);
+    return OTGAN_ERR_WORKSPACE;
+  }
+  hipStream_t s = (hipStream_t)stream;
+  if (wino_s2_ok(d, g)) {
+    rc = WINO(wino_s2_prepare_filters_raw)(wino_s2_geo(d, g), which, V, scale, (float*)filters, s);
+  } else if (!wino_ok(d, g) && wino_up3_ok(d, g)) {
+    if (which == 3) {
+      WinoS2Geo wg = wino_up3_wgrad_geo(d, g);
+      wg.w_amax = d->w_amax;     // (same value as the reduction of w that the route through w runs here)
+      rc = WINO(wino_s2_prepare_filters_raw)(wg, 1, V, scale, (float*)filters, s);
+    } else {
+      rc = WINO(wino_up3_prepare_filters_raw)(wino_up3_geo(d, g), V, scale, (float*)filters, s);
+    }
+  } else {
+    if (which < 2) {
+      otgan_set_error("which = %d takes the FOLDED weights of this layer: no route from the raw weights", which);
+      return OTGAN_ERR_UNSUPPORTED;
+    }
+    rc = WINO(wino_prepare_filters_raw)(wino_geo(d), which, V, scale, (float*)filters, s);
+  }
+  OTGAN_CHECK_LAUNCH("conv2d prepare filters (raw)");
+  return rc;
+}
+
 static int conv2d_fwd_impl(const otgan_conv_desc* d, const float* x, const int32_t* cmap, const float* wT,
                            const float* filters, const float* bias, float* y, void* workspace,
                            size_t workspace_bytes, void* stream);

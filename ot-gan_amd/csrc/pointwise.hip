@@ -20,11 +20,11 @@ inline int grid_for(long n, int per_thread = 4) {
 // ---- column reductions: partial[chunk][c] = sum_{r in chunk} op(a[r][c], b[r][c]) ----------
 // OP 0: a, 1: a*a, 2: a*b.   Block = 256 threads: lane = column (64 per block), 4 waves split
 // the chunk's rows; coalesced 256-byte row segments.
-template <int OP>
-__global__ __launch_bounds__(256) void colreduce_kernel(const float* __restrict__ a,
-                                                        const float* __restrict__ b, long rows,
-                                                        int cols, long lda,
-                                                        float* __restrict__ partial) {
+// CMAX (OP 1 only): the same pass also keeps pmax[chunk][c] = max_{r in chunk} |a[r][c]| as a bit pattern (common.h: amax_bits)
+template <int OP, bool CMAX>
+__device__ __forceinline__ void colreduce_body(const float* __restrict__ a, const float* __restrict__ b, long rows,
+                                               int cols, long lda, float* __restrict__ partial,
+                                               unsigned* __restrict__ pmax) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int c = blockIdx.x * 64 + lane;
   const int chunk = blockIdx.y;
@@ -33,12 +33,17 @@ __global__ __launch_bounds__(256) void colreduce_kernel(const float* __restrict_
   long r1 = r0 + per;
   if (r1 > rows) r1 = rows;
   float s = 0.f;
+  unsigned m = 0u;
   if (c < cols) {
     for (long r = r0 + wave; r < r1; r += 4) {
       const float av = a[r * lda + c];
       if (OP == 0) s += av;
       else if (OP == 1) s += av * av;
       else s += av * b[r * lda + c];
+      if constexpr (CMAX) {
+        const unsigned ab = amax_bits(av);
+        m = ab > m ? ab : m;
+      }
     }
   }
   __shared__ float red[4][64];
@@ -46,6 +51,27 @@ __global__ __launch_bounds__(256) void colreduce_kernel(const float* __restrict_
   __syncthreads();
   if (wave == 0 && c < cols)
     partial[(long)chunk * cols + c] = (red[0][lane] + red[1][lane]) + (red[2][lane] + red[3][lane]);
+  if constexpr (CMAX) {     // (nothing of this exists in the kernels without it)
+    __shared__ unsigned redm[4][64];
+    redm[wave][lane] = m;
+    __syncthreads();
+    if (wave == 0 && c < cols) {
+#pragma unroll
+      for (int k = 1; k < 4; ++k) m = redm[k][lane] > m ? redm[k][lane] : m;
+      pmax[(long)chunk * cols + c] = m;
+    }
+  }
+}
+template <int OP>
+__global__ __launch_bounds__(256) void colreduce_kernel(const float* __restrict__ a,
+                                                        const float* __restrict__ b, long rows,
+                                                        int cols, long lda,
+                                                        float* __restrict__ partial) {
+  colreduce_body<OP, false>(a, b, rows, cols, lda, partial, nullptr);
+}
+__global__ __launch_bounds__(256) void colsq_cmax_kernel(const float* __restrict__ a, long rows, int cols, long lda,
+                                                         float* __restrict__ partial, unsigned* __restrict__ pmax) {
+  colreduce_body<1, true>(a, nullptr, rows, cols, lda, partial, pmax);
 }
 
 // MODE 0: out = sum; 1: out = rsqrt(max(sum, 1e-12))  (tf.nn.l2_normalize epsilon, nn.py:176)
@@ -70,11 +96,10 @@ __global__ __launch_bounds__(256) void colreduce_finish_kernel(const float* __re
 
 // float4 variant: a block covers 64 columns (16 lanes x float4) and 16 row lanes
 // (4 per wave), i.e. every wave-load moves 4 rows x 256 bytes.
-template <int OP>
-__global__ __launch_bounds__(256) void colreduce4_kernel(const float* __restrict__ a,
-                                                         const float* __restrict__ b, long rows,
-                                                         int cols, long lda,
-                                                         float* __restrict__ partial) {
+template <int OP, bool CMAX>
+__device__ __forceinline__ void colreduce4_body(const float* __restrict__ a, const float* __restrict__ b, long rows,
+                                                int cols, long lda, float* __restrict__ partial,
+                                                unsigned* __restrict__ pmax) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int cq = lane & 15, rsub = (lane >> 4) + 4 * wave;  // 16 column quads x 16 row lanes
   const int c = blockIdx.x * 64 + 4 * cq;
@@ -84,6 +109,7 @@ __global__ __launch_bounds__(256) void colreduce4_kernel(const float* __restrict
   long r1 = r0 + per;
   if (r1 > rows) r1 = rows;
   float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
+  uint4 m = make_uint4(0u, 0u, 0u, 0u);
   if (c < cols) {
     for (long r = r0 + rsub; r < r1; r += 16) {
       const float4 av = *reinterpret_cast<const float4*>(a + r * lda + c);
@@ -94,6 +120,10 @@ __global__ __launch_bounds__(256) void colreduce4_kernel(const float* __restrict
       } else {
         const float4 bv = *reinterpret_cast<const float4*>(b + r * lda + c);
         s.x += av.x * bv.x; s.y += av.y * bv.y; s.z += av.z * bv.z; s.w += av.w * bv.w;
+      }
+      if constexpr (CMAX) {
+        const unsigned bx = amax_bits(av.x), by = amax_bits(av.y), bz = amax_bits(av.z), bw = amax_bits(av.w);
+        m.x = bx > m.x ? bx : m.x; m.y = by > m.y ? by : m.y; m.z = bz > m.z ? bz : m.z; m.w = bw > m.w ? bw : m.w;
       }
     }
   }
@@ -110,11 +140,37 @@ __global__ __launch_bounds__(256) void colreduce4_kernel(const float* __restrict
     const int cc = blockIdx.x * 64 + 4 * threadIdx.x;
     *reinterpret_cast<float4*>(partial + (long)chunk * cols + cc) = t;
   }
+  if constexpr (CMAX) {     // (nothing of this exists in the kernels without it)
+    __shared__ uint4 redm[16][17];
+    redm[rsub][cq] = m;
+    __syncthreads();
+    if (threadIdx.x < 16 && c < cols) {
+      uint4 u = make_uint4(0u, 0u, 0u, 0u);
+#pragma unroll
+      for (int k = 0; k < 16; ++k) {
+        const uint4 v = redm[k][threadIdx.x];
+        u.x = v.x > u.x ? v.x : u.x; u.y = v.y > u.y ? v.y : u.y; u.z = v.z > u.z ? v.z : u.z; u.w = v.w > u.w ? v.w : u.w;
+      }
+      *reinterpret_cast<uint4*>(pmax + (long)chunk * cols + (blockIdx.x * 64 + 4 * threadIdx.x)) = u;
+    }
+  }
+}
+template <int OP>
+__global__ __launch_bounds__(256) void colreduce4_kernel(const float* __restrict__ a,
+                                                         const float* __restrict__ b, long rows,
+                                                         int cols, long lda,
+                                                         float* __restrict__ partial) {
+  colreduce4_body<OP, false>(a, b, rows, cols, lda, partial, nullptr);
+}
+__global__ __launch_bounds__(256) void colsq_cmax4_kernel(const float* __restrict__ a, long rows, int cols, long lda,
+                                                          float* __restrict__ partial, unsigned* __restrict__ pmax) {
+  colreduce4_body<1, true>(a, nullptr, rows, cols, lda, partial, pmax);
 }
 
+// pmax (OP 1 only): also the column maxima of |a| per chunk, pmax[chunk][c] (same grid, same sums)
 template <int OP>
 int colreduce(const float* a, const float* b, long rows, int cols, long lda, float* partial,
-              int* nchunk_out, hipStream_t s) {
+              int* nchunk_out, hipStream_t s, unsigned* pmax = nullptr) {
   const int colblocks = ceil_div(cols, 64);
   long nchunk = ceil_div(1024, colblocks);              // aim for >= 1024 workgroups
   if (nchunk > kChunks) nchunk = kChunks;
@@ -123,8 +179,12 @@ int colreduce(const float* a, const float* b, long rows, int cols, long lda, flo
   dim3 grid(colblocks, (int)nchunk);
   const bool vec = (cols % 4 == 0) && (lda % 4 == 0) && ((reinterpret_cast<uintptr_t>(a) & 15) == 0) &&
                    (!b || (reinterpret_cast<uintptr_t>(b) & 15) == 0) &&
-                   ((reinterpret_cast<uintptr_t>(partial) & 15) == 0);
-  if (vec) hipLaunchKernelGGL(colreduce4_kernel<OP>, grid, dim3(256), 0, s, a, b, rows, cols, lda, partial);
+                   ((reinterpret_cast<uintptr_t>(partial) & 15) == 0) &&
+                   ((reinterpret_cast<uintptr_t>(pmax) & 15) == 0);
+  if (pmax) {
+    if (vec) hipLaunchKernelGGL(colsq_cmax4_kernel, grid, dim3(256), 0, s, a, rows, cols, lda, partial, pmax);
+    else hipLaunchKernelGGL(colsq_cmax_kernel, grid, dim3(256), 0, s, a, rows, cols, lda, partial, pmax);
+  } else if (vec) hipLaunchKernelGGL(colreduce4_kernel<OP>, grid, dim3(256), 0, s, a, b, rows, cols, lda, partial);
   else hipLaunchKernelGGL(colreduce_kernel<OP>, grid, dim3(256), 0, s, a, b, rows, cols, lda, partial);
   *nchunk_out = (int)nchunk;
   OTGAN_CHECK_LAUNCH("colreduce");
@@ -166,6 +226,44 @@ __global__ __launch_bounds__(256) void weightnorm_apply_kernel(const float* __re
   }
   // amax record of the normalised weights (the Winograd filter operands are scaled by it: otgan_conv_desc::w_amax)
   if (rec) amax_commit(rec, mb);
+}
+
+// colreduce_finish_kernel<1> (same sums, same order) for a caller that never writes w: inv[c], scale[c] = g[c] * inv[c] (the
+// factor weightnorm_apply_kernel multiplies V by) and the amax record of w = V * scale from the column maxima of |V|:
+// rounding is monotone, so max_k |V[k][c] * scale[c]| == |max_k |V[k][c]| * scale[c]| bit for bit (a NaN or an infinity in
+// the column stays one: inf * 0 = NaN, as in w itself).
+__global__ __launch_bounds__(256) void weightnorm_scale_finish_kernel(const float* __restrict__ partial,
+                                                                      const unsigned* __restrict__ pmax, int nchunk,
+                                                                      int cols, const float* __restrict__ g,
+                                                                      float* __restrict__ inv, float* __restrict__ scale,
+                                                                      float* __restrict__ rec) {
+  const int lane = threadIdx.x & 63, part = threadIdx.x >> 6;
+  const int c = blockIdx.x * 64 + lane;
+  float s = 0.f;
+  unsigned m = 0u;
+  if (c < cols)
+    for (int k = part; k < nchunk; k += 4) {
+      s += partial[(long)k * cols + c];
+      const unsigned b = pmax[(long)k * cols + c];
+      m = b > m ? b : m;
+    }
+  __shared__ float red[4][64];
+  __shared__ unsigned redm[4][64];
+  red[part][lane] = s;
+  redm[part][lane] = m;
+  __syncthreads();
+  unsigned mb = 0u;
+  if (part == 0 && c < cols) {
+    const float t = (red[0][lane] + red[1][lane]) + (red[2][lane] + red[3][lane]);
+    const float iv = rsqrtf(fmaxf(t, 1e-12f));
+    const float sc = __fmul_rn(g[c], iv);
+#pragma unroll
+    for (int k = 1; k < 4; ++k) m = redm[k][lane] > m ? redm[k][lane] : m;
+    inv[c] = iv;
+    scale[c] = sc;
+    mb = amax_bits(__fmul_rn(__uint_as_float(m), sc));
+  }
+  amax_commit(rec, mb);     // (every thread of the workgroup arrives here)
 }
 
 // dV = g*inv*(dw - V*dot*inv^2),  dg = dot*inv,  dot[c] = sum_k dw[k][c] V[k][c]
@@ -776,6 +874,31 @@ int otgan_weightnorm_fwd_amax_f32(const float* V, const float* g, int K, int Cou
   dim3 grid(ceil_div(Cout, 32), ceil_div(K, 32));
   hipLaunchKernelGGL(weightnorm_apply_kernel, grid, dim3(256), 0, s, V, g, inv_norm, K, Cout, w, wT, w_amax);
   OTGAN_CHECK_LAUNCH("weightnorm fwd");
+  return OTGAN_OK;
+}
+size_t otgan_weightnorm_scale_scratch_floats(int K, int Cout) {
+  if (K <= 0 || Cout <= 0) return 0;
+  long nchunk = ceil_div_l(K, 64);
+  if (nchunk > kChunks) nchunk = kChunks;
+  return 2 * (size_t)nchunk * Cout;
+}
+int otgan_weightnorm_scale_amax_f32(const float* V, const float* g, int K, int Cout, float* inv_norm, float* scale,
+                                    float* w_amax, float* scratch, size_t scratch_floats, void* stream) {
+  OTGAN_CHECK_ARG(V && g && inv_norm && scale && w_amax && scratch && K > 0 && Cout > 0, "bad arguments");
+  OTGAN_CHECK_ARG((reinterpret_cast<uintptr_t>(scratch) & 15) == 0 && scratch_floats >= otgan_weightnorm_scale_scratch_floats(K, Cout),
+                  "scratch misaligned or smaller than otgan_weightnorm_scale_scratch_floats");
+  hipStream_t s = (hipStream_t)stream;
+  ProfScope ps(OTGAN_PROF_POINTWISE, 0.0, 4.0 * (double)K * Cout, s);
+  // partial[nchunk][Cout] sums, then pmax[nchunk][Cout] maxima, nchunk as colreduce() chooses it (<= the bound above)
+  long bound = ceil_div_l(K, 64);
+  if (bound > kChunks) bound = kChunks;
+  unsigned* pmax = reinterpret_cast<unsigned*>(scratch + (size_t)bound * Cout);
+  int nchunk = 0;
+  int rc = colreduce<1>(V, nullptr, K, Cout, Cout, scratch, &nchunk, s, pmax);
+  if (rc) return rc;
+  hipLaunchKernelGGL(weightnorm_scale_finish_kernel, dim3(ceil_div(Cout, 64)), dim3(256), 0, s, scratch, pmax, nchunk,
+                     Cout, g, inv_norm, scale, w_amax);
+  OTGAN_CHECK_LAUNCH("weightnorm scale");
   return OTGAN_OK;
 }
 int otgan_weightnorm_fwd_f32(const float* V, const float* g, int K, int Cout, float* w, float* wT, float* inv_norm,

@@ -712,6 +712,129 @@ __global__ __launch_bounds__(256) void wino_filter_bwd_unfolded_kernel(const flo
   tf_filter(g, [&](int f, f32x4 v) { st_operand(U, P, Cin, 4 * Cout, f, ci, cls * Cout + co, v, hdr_scale(P, f)); });
 }
 
+// ---- the same operands from the RAW weight-norm direction V[tap][ci][co] (HWIO) and scale[co] = g[co] * inv_norm[co] ----
+// The normalised weight is formed in registers as weightnorm_apply_kernel rounds it, V * (g * inv): one fp32 multiply that
+// must not fuse with the fold additions behind it (an FMA changes low bits; the operands are held bit-identical to the
+// ones made from the normalised copies w / wT, which these kernels never read).
+__device__ __forceinline__ f32x4 wn_mul4(f32x4 v, f32x4 sc) {
+#pragma clang fp contract(off)
+  return v * sc;
+}
+// four consecutive ci of one co: the operand is ci-contiguous, V co-contiguous
+__device__ __forceinline__ f32x4 wn_gather4(const float* __restrict__ p, long stride, float sc) {
+  const f32x4 v = {p[0], p[stride], p[2 * stride], p[3 * stride]};
+  const f32x4 s = {sc, sc, sc, sc};
+  return wn_mul4(v, s);
+}
+// Operands whose ROWS run along V's contiguous axis (the forward ones).  A wave makes 16 rows x 16 k.  It LOADS with lane =
+// (row = lane & 15, k quad = lane >> 4): sixteen consecutive lanes read 64 contiguous bytes of a row of V; it folds there,
+// then every lane fetches the folded taps of the lane that holds what it STORES -- lane = (k quad = lane & 3, row = lane >> 2),
+// op_thread's order, 512 contiguous bytes per store -- through the LDS crossbar (ds_bpermute: no memory, no barrier).  Both
+// layouts give a lane one row and four consecutive k, so the exchange is a permutation of lanes.
+// A workgroup = `halves` (blockDim.x / 256) strips of 16 rows x four groups of 16 k; two strips take whole 128-byte lines
+// of V.  quads = groups per workgroup that are distinct k (4), or 1 when the four waves of a strip are the four classes of
+// ONE group (un-folded layers: the classes fold the same taps at the same time, V comes from HBM once).  All results are
+// wave-uniform: a wave leaves whole, so every lane is there for the exchange.
+__device__ __forceinline__ bool raw_wave(long rows, int ngroups, int quads, long& row0, int& group, int& sub) {
+  const int per = (ngroups + quads - 1) / quads, halves = blockDim.x >> 8;
+  const int wave = threadIdx.x >> 6;
+  sub = wave & 3;
+  group = (int)(blockIdx.x % per) * quads + (quads == 4 ? sub : 0);
+  row0 = (long)(blockIdx.x / per) * (16 * halves) + (wave >> 2) * 16;
+  return row0 < rows && group < ngroups;
+}
+__device__ __forceinline__ f32x4 raw_to_store_lane(f32x4 v) {
+  const int lane = threadIdx.x & 63, src = (lane & 3) * 16 + ((lane >> 2) & 15);
+  f32x4 r;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) r[k] = __int_as_float(__builtin_amdgcn_ds_bpermute(src << 2, __float_as_int(v[k])));
+  return r;
+}
+// Strips of 32 rows (512 threads) while that leaves kRawMinWorkgroups, two for each of the 256 compute units, else of 16.
+// The 256-channel generator layer would get 128 workgroups of 512 -- half the compute units idle: 21.0 us against the 18.2 us
+// of the kernel on wT, which ran 256 workgroups (profiles/filters_from_raw_ab.txt); the 512-channel layers sit at the
+// threshold with 512 and take the same time either way.
+constexpr int kRawMinWorkgroups = 512;
+inline int raw_halves(long rows, int ngroups, int quads) {
+  return ((rows + 31) / 32) * ((ngroups + quads - 1) / quads) >= kRawMinWorkgroups ? 2 : 1;
+}
+inline int raw_grid(long rows, int ngroups, int quads, int halves) {
+  return (int)(((rows + 16 * halves - 1) / (16 * halves)) * ((ngroups + quads - 1) / quads));
+}
+
+// U[f][cls*Cout + co][ci]
+__global__ __launch_bounds__(512) void wino_filter_fwd_raw_kernel(const float* __restrict__ V, const float* __restrict__ scale,
+                                                                int Cin, int Cout, float* __restrict__ U, u16* P) {
+  long co0;
+  int grp, cls;
+  if (!raw_wave(Cout, Cin >> 4, 1, co0, grp, cls)) return;
+  const int lane = threadIdx.x & 63;
+  const int ph = cls >> 1, pw = cls & 1;
+  f32x4 g[3][3];
+  {
+    long co = co0 + (lane & 15);
+    if (co >= Cout) co = Cout - 1;       // (a partly filled strip: in bounds, never stored)
+    const float* src = V + (long)(grp * 16 + (lane >> 4) * 4) * Cout + co;
+    const float sc = scale[co];
+    const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+      for (int j = 0; j < 3; ++j) g[i][j] = zero;
+#pragma unroll
+    for (int kh = 0; kh < 5; ++kh)
+#pragma unroll
+      for (int kw = 0; kw < 5; ++kw) {
+        const f32x4 v = wn_gather4(src + (long)(kh * 5 + kw) * Cin * Cout, Cout, sc);
+#pragma unroll
+        for (int i = 0; i < 3; ++i)
+#pragma unroll
+          for (int j = 0; j < 3; ++j)
+            if (fold5_tap(ph, kh) == i && fold5_tap(pw, kw) == j) g[i][j] += v;
+      }
+  }
+#pragma unroll
+  for (int i = 0; i < 3; ++i)
+#pragma unroll
+    for (int j = 0; j < 3; ++j) g[i][j] = raw_to_store_lane(g[i][j]);
+  const long co = co0 + ((lane >> 2) & 15);
+  if (co >= Cout) return;
+  const int ci = grp * 16 + (lane & 3) * 4;
+  const long rows = 4L * Cout, row = cls * (long)Cout + co;
+  tf_filter(g, [&](int f, f32x4 v) { st_operand(U, P, rows, Cin, f, row, ci, v, hdr_scale(P, f)); });
+}
+
+// U'[f][ci][cls*Cout + co] (flipped taps): V is laid out as w is
+__global__ __launch_bounds__(256) void wino_filter_bwd_raw_kernel(const float* __restrict__ V, const float* __restrict__ scale,
+                                                                int Cin, int Cout, float* __restrict__ U, u16* P) {
+  const int c4n = Cout >> 2;
+  long row;
+  int k4;
+  if (!op_thread(P != nullptr, Cin, 4 * c4n, row, k4)) return;
+  const int ci = (int)row, cls = k4 / c4n, co = (k4 % c4n) * 4;
+  const int ph = cls >> 1, pw = cls & 1;
+  const float* src = V + (long)ci * Cout + co;
+  const f32x4 sc = ld4(scale + co);
+  const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
+  f32x4 g[3][3];
+#pragma unroll
+  for (int i = 0; i < 3; ++i)
+#pragma unroll
+    for (int j = 0; j < 3; ++j) g[i][j] = zero;
+#pragma unroll
+  for (int kh = 0; kh < 5; ++kh)
+#pragma unroll
+    for (int kw = 0; kw < 5; ++kw) {
+      const f32x4 v = wn_mul4(ld4(src + (long)(kh * 5 + kw) * Cin * Cout), sc);
+#pragma unroll
+      for (int i = 0; i < 3; ++i)
+#pragma unroll
+        for (int j = 0; j < 3; ++j)
+          if (fold5_tap(ph, kh) == 2 - i && fold5_tap(pw, kw) == 2 - j) g[i][j] += v;
+    }
+  tf_filter(g, [&](int f, f32x4 v) { st_operand(U, P, Cin, 4 * Cout, f, ci, cls * Cout + co, v, hdr_scale(P, f)); });
+}
+
 // dweff[cls][tap][ci][co] = (G^T dU G)[tap],  dU[f] = sum over splits of slab[split][f][ci][cls*Cout + co]
 __global__ __launch_bounds__(256) void wino_filter_adj_kernel(const float* __restrict__ slabs, int nsplit,
                                                             long split_stride, int Cin, int Cout,
@@ -872,6 +995,76 @@ __global__ __launch_bounds__(256) void wino_s2_filter_bwd_kernel(const float* __
     for (int j = 0; j < 3; ++j) {
       const int kh = plain ? 2 - i : s2_tap(pi, 2 - i), kw = plain ? 2 - j : s2_tap(pj, 2 - j);
       g[i][j] = (kh >= 0 && kw >= 0) ? ld4(w + ((long)(kh * kk + kw) * Ceff + ce) * Cout + co) : zero;
+    }
+  tf_filter(g, [&](int f, f32x4 v) { st_operand(U, P, rows, Kp, f, r, co, v, hdr_scale(P, f)); });
+}
+
+// the same two operands from the raw V[kh*kk+kw][ce][co] and scale[co] (wn_mul4, above)
+// forward: U[f][co][cls*Ceff + ce]
+__global__ __launch_bounds__(512) void wino_s2_filter_fwd_raw_kernel(const float* __restrict__ V, const float* __restrict__ scale,
+                                                                   int Ceff, int Cout, float* __restrict__ U, u16* P, int plain,
+                                                                   int ld) {
+  const int ncls = plain ? 1 : 4, kk = plain ? 3 : 5;
+  long co0;
+  int grp, sub;
+  if (!raw_wave(Cout, (ncls * Ceff) >> 4, 4, co0, grp, sub)) return;
+  const int lane = threadIdx.x & 63;
+  const int cls = grp * 16 / Ceff, ce0 = grp * 16 % Ceff;      // (Ceff % 16 == 0: a group lies in one class)
+  const int pi = cls >> 1, pj = cls & 1;
+  f32x4 g[3][3];
+  {
+    long co = co0 + (lane & 15);
+    if (co >= Cout) co = Cout - 1;       // (a partly filled strip: in bounds, never stored)
+    const float* src = V + (long)(ce0 + (lane >> 4) * 4) * Cout + co;
+    const float sc = scale[co];
+    const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+      for (int j = 0; j < 3; ++j) {
+        const int kh = plain ? i : s2_tap(pi, i), kw = plain ? j : s2_tap(pj, j);
+        g[i][j] = (kh >= 0 && kw >= 0) ? wn_gather4(src + (long)(kh * kk + kw) * Ceff * Cout, Cout, sc) : zero;
+      }
+  }
+#pragma unroll
+  for (int i = 0; i < 3; ++i)
+#pragma unroll
+    for (int j = 0; j < 3; ++j) g[i][j] = raw_to_store_lane(g[i][j]);
+  const int co = (int)co0 + ((lane >> 2) & 15);
+  if (co >= Cout) return;
+  const int ce = ce0 + (lane & 3) * 4;
+  tf_filter(g, [&](int f, f32x4 v) {
+    if (plain || s2_present(cls, f, 0))   // absent blocks are never read by the GEMM
+      st_operand(U, P, Cout, ld, f, co, cls * Ceff + ce, v, hdr_scale(P, f));
+  });
+}
+
+// backward (flipped): U'[f][cls*Ceff + ce][co]
+__global__ __launch_bounds__(256) void wino_s2_filter_bwd_raw_kernel(const float* __restrict__ V, const float* __restrict__ scale,
+                                                                   int Ceff, int Cout, float* __restrict__ U, u16* P, int plain,
+                                                                   int Kp) {
+  long r;                               // cls*Ceff + ce
+  int k4;
+  const long rows = (plain ? 1L : 4L) * Ceff;
+  const int kk = plain ? 3 : 5;
+  if (!op_thread(P != nullptr, rows, Kp >> 2, r, k4)) return;
+  const int co = k4 * 4;
+  if (co >= Cout) {   // K padding: zero columns [Cout, Kp)
+    const f32x4 z = {0.f, 0.f, 0.f, 0.f};
+    for (int f = 0; f < WF; ++f) st_operand(U, P, rows, Kp, f, r, co, z, 1.f);
+    return;
+  }
+  const int ce = (int)(r % Ceff), cls = (int)(r / Ceff);
+  const int pi = cls >> 1, pj = cls & 1;
+  const f32x4 sc = ld4(scale + co);
+  const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
+  f32x4 g[3][3];
+#pragma unroll
+  for (int i = 0; i < 3; ++i)
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+      const int kh = plain ? 2 - i : s2_tap(pi, 2 - i), kw = plain ? 2 - j : s2_tap(pj, 2 - j);
+      g[i][j] = (kh >= 0 && kw >= 0) ? wn_mul4(ld4(V + ((long)(kh * kk + kw) * Ceff + ce) * Cout + co), sc) : zero;
     }
   tf_filter(g, [&](int f, f32x4 v) { st_operand(U, P, rows, Kp, f, r, co, v, hdr_scale(P, f)); });
 }
@@ -1448,6 +1641,24 @@ int wino_prepare_filters(const WinoGeo& g, int which, const float* w, long cls_s
   return OTGAN_OK;
 }
 
+// which = 2 / 3 from the raw direction tensor V[25][Cin][Cout] and scale[Cout]; the scales from g.w_amax (required)
+int wino_prepare_filters_raw(const WinoGeo& g, int which, const float* V, const float* scale, float* out, hipStream_t s) {
+  const int N4 = 4 * g.Cout;
+  if (which == 2) {
+    const bool x3 = use_x3() && g.Cin % X3_BK == 0;
+    if (x3) op_scales(V, 1, 25 * g.Cin * g.Cout, 0, out, kGainG, 4.f, false, s, g.w_amax);
+    const int hv = raw_halves(g.Cout, g.Cin / 16, 1);
+    hipLaunchKernelGGL(wino_filter_fwd_raw_kernel, dim3(raw_grid(g.Cout, g.Cin / 16, 1, hv)), dim3(256 * hv), 0, s, V, scale,
+                       g.Cin, g.Cout, out, x3 ? op_planes(out) : nullptr);
+  } else {
+    const bool x3 = use_x3() && N4 % X3_BK == 0;
+    if (x3) op_scales(V, 1, 25 * g.Cin * g.Cout, 0, out, kGainG, 4.f, false, s, g.w_amax);
+    hipLaunchKernelGGL(wino_filter_bwd_raw_kernel, dim3(op_grid(g.Cin, g.Cout)), dim3(256), 0, s, V, scale, g.Cin, g.Cout,
+                       out, x3 ? op_planes(out) : nullptr);
+  }
+  return OTGAN_OK;
+}
+
 int wino_fwd(const WinoGeo& g, const float* x, const float* weffT, long cls_stride, const float* bias, float* y,
              float* ws, hipStream_t s, const float* prep) {
   const long T = wino_tiles(g);
@@ -1739,6 +1950,28 @@ int wino_s2_prepare_filters(const WinoS2Geo& g, int which, const float* w, float
   return OTGAN_OK;
 }
 
+// the same from the raw V[taps][Ceff][Cout] and scale[Cout]; the scales from g.w_amax (required)
+int wino_s2_prepare_filters_raw(const WinoS2Geo& g, int which, const float* V, const float* scale, float* out, hipStream_t s) {
+  if (which == 0) {
+    const int Kf = s2_kf(g);
+    const bool x3 = use_x3() && Kf % X3_BK == 0 && (g.plain || g.Ceff % X3_BK == 0);
+    if (x3) op_scales(V, 1, s2_taps(g) * g.Ceff * g.Cout, 0, out, kGainG, 1.f, false, s, g.w_amax);
+    const int hv = raw_halves(g.Cout, s2_k(g) / 16, 4);
+    hipLaunchKernelGGL(wino_s2_filter_fwd_raw_kernel, dim3(raw_grid(g.Cout, s2_k(g) / 16, 4, hv)), dim3(256 * hv), 0, s, V, scale,
+                       g.Ceff, g.Cout, out, x3 ? op_planes(out) : nullptr, g.plain, x3 ? Kf : s2_k(g));
+    if (x3 && Kf > s2_k(g))
+      hipLaunchKernelGGL(op_zero_cols_kernel, dim3(op_grid(g.Cout, (Kf - s2_k(g)) / 4)), dim3(256), 0, s, op_planes(out),
+                         (long)g.Cout, Kf, s2_k(g), Kf);
+  } else {
+    const int Kp = s2_kp(g);
+    const bool x3 = use_x3() && Kp % X3_BK == 0;
+    if (x3) op_scales(V, 1, s2_taps(g) * g.Ceff * g.Cout, 0, out, kGainG, 1.f, false, s, g.w_amax);
+    hipLaunchKernelGGL(wino_s2_filter_bwd_raw_kernel, dim3(op_grid(s2_k(g), Kp / 4)), dim3(256), 0, s, V, scale, g.Ceff,
+                       g.Cout, out, x3 ? op_planes(out) : nullptr, g.plain, Kp);
+  }
+  return OTGAN_OK;
+}
+
 int wino_s2_fwd(const WinoS2Geo& g, const float* x, const float* wT, const float* bias, float* y, float* ws,
                 hipStream_t s, const float* prep) {
   const long T = wino_s2_tiles(g);
@@ -1923,6 +2156,14 @@ int wino_up3_prepare_filters(const WinoUp3Geo& g, const float* wT, float* out, h
   op_scales(wT, 1, 9 * g.Ceff * g.Cout, 0, out, kGainG, 1.f, false, s, g.w_amax);
   hipLaunchKernelGGL(wino_up3_filter_fwd_kernel, dim3(op_grid(g.Cout, g.Ceff / 4)), dim3(256), 0, s, wT, g.Ceff, g.Cout, out,
                      op_planes(out));
+  return OTGAN_OK;
+}
+// from the raw V[9][Ceff][Cout] and scale[Cout]: the one-class forward kernel of the strided layers, same operand
+int wino_up3_prepare_filters_raw(const WinoUp3Geo& g, const float* V, const float* scale, float* out, hipStream_t s) {
+  op_scales(V, 1, 9 * g.Ceff * g.Cout, 0, out, kGainG, 1.f, false, s, g.w_amax);
+  const int hv = raw_halves(g.Cout, g.Ceff / 16, 4);
+  hipLaunchKernelGGL(wino_s2_filter_fwd_raw_kernel, dim3(raw_grid(g.Cout, g.Ceff / 16, 4, hv)), dim3(256 * hv), 0, s, V, scale,
+                     g.Ceff, g.Cout, out, op_planes(out), 1, g.Ceff);
   return OTGAN_OK;
 }
 int wino_up3_fwd(const WinoUp3Geo& g, const float* x, const float* bias, float* y, float* ws, hipStream_t s,

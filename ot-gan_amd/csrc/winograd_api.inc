@@ -33,4 +33,9 @@ size_t wino_up3_filter_floats(const WinoUp3Geo& g);
 int wino_up3_prepare_filters(const WinoUp3Geo& g, const float* wT, float* out, hipStream_t s);
 int wino_up3_fwd(const WinoUp3Geo& g, const float* x, const float* bias, float* y, float* ws, hipStream_t s,
                  const float* prep);
+// the same operands from the raw weight-norm direction V (HWIO) and scale[Cout] = g * inv_norm, bit-identical to the ones made
+// from the normalised copies (which is then never written); un-folded sources only (wino: which = 2 / 3), w_amax required
+int wino_prepare_filters_raw(const WinoGeo& g, int which, const float* V, const float* scale, float* out, hipStream_t s);
+int wino_s2_prepare_filters_raw(const WinoS2Geo& g, int which, const float* V, const float* scale, float* out, hipStream_t s);
+int wino_up3_prepare_filters_raw(const WinoUp3Geo& g, const float* V, const float* scale, float* out, hipStream_t s);
 }  // namespace WINO_NS

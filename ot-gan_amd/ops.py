@@ -207,6 +207,31 @@ def weightnorm_fwd(V2d, g):
     return w, wT, inv
 
 
+# Layers whose forward AND input-gradient passes take Winograd filters made from un-folded weights: both filter operands
+# straight from (V, g * inv_norm); the normalised copies w / wT are never written (Conv2dFunction.forward).  False: through
+# weightnorm_fwd, as every other layer (same bits; tests/test_filters_from_raw_gpu.py compares the two).
+FILTERS_FROM_RAW = True
+
+
+def weightnorm_scale(V2d, g):
+    """Weight norm without the normalised weights.  Returns (scale, inv_norm): scale = g * inv_norm [Cout] stands in for
+    w = V2d * scale -- it carries the amax record of that w and, as "raw", V2d itself; prepare_filters() makes the filters
+    from the pair."""
+    K, Cout = V2d.shape
+    L = _lib.lib()
+    inv = torch.empty(Cout, dtype=V2d.dtype, device=V2d.device)
+    scale = torch.empty(Cout, dtype=V2d.dtype, device=V2d.device)
+    rec = amax_slot(V2d.device)
+    n = L.otgan_weightnorm_scale_scratch_floats(K, Cout)
+    scratch = torch.empty(n, dtype=torch.float32, device=V2d.device)
+    _lib.check(L.otgan_weightnorm_scale_amax_f32(V2d.data_ptr(), g.data_ptr(), K, Cout, inv.data_ptr(), scale.data_ptr(),
+                                                 rec.data_ptr(), scratch.data_ptr(), n, _lib.stream_ptr()),
+               "weightnorm_scale")
+    tag_amax(scale, rec)
+    leave(scale, "raw", V2d)
+    return scale, inv
+
+
 def weightnorm_bwd(V2d, g, inv, dw):
     K, Cout = V2d.shape
     dV = torch.empty_like(V2d)
@@ -428,7 +453,8 @@ def shared_x_operand(desc, device):
 
 def prepare_filters(desc, which, w, **fields):
     """Winograd-domain filters of a layer's forward (which=0, from wT) or dgrad (which=1, from w) pass, or None
-    when the pass does not run as a Winograd GEMM (otgan_layers.h).  w_amax is the record `w` carries unless given."""
+    when the pass does not run as a Winograd GEMM (otgan_layers.h).  w_amax is the record `w` carries unless given.
+    `w` may be the scale of weightnorm_scale(): the filters then come from the raw V it carries, same bits."""
     L = _lib.lib()
     # left by weightnorm_fwd on the un-folded w / wT (folded weights are another tensor: no record, the kernel reduces them)
     fields.setdefault("w_amax", amax_of(w))
@@ -437,6 +463,12 @@ def prepare_filters(desc, which, w, **fields):
     if not nbytes:
         return None
     buf = torch.empty((nbytes + 3) // 4, dtype=torch.float32, device=w.device)
+    raw = take(w, "raw")
+    if raw is not None:
+        _lib.check(L.otgan_conv2d_prepare_filters_raw_f32(ctypes.byref(desc), which, raw.data_ptr(), w.data_ptr(),
+                                                          buf.data_ptr(), buf.numel() * 4, _lib.stream_ptr()),
+                   "prepare_filters_raw")
+        return buf
     _lib.check(L.otgan_conv2d_prepare_filters_f32(ctypes.byref(desc), which, w.data_ptr(), buf.data_ptr(),
                                                   buf.numel() * 4, _lib.stream_ptr()), "prepare_filters")
     return buf
@@ -556,13 +588,27 @@ class Conv2dFunction(torch.autograd.Function):
         cmap, inv = channel_maps(segs if (segs and not upsample) else (C,), preact, x.device)
         nfold = _lib.lib().otgan_conv2d_folded_weight_elems(ctypes.byref(desc))
 
-        def compute():
+        def has(which):
+            return _lib.lib().otgan_conv2d_filter_bytes(ctypes.byref(desc), which) > 0
+
+        # Winograd passes of a folded layer take filters made from the UN-folded weights (which = 2 forward,
+        # 3 dgrad: no fold pass at all); a layer may have only the forward one (3x3 on an upsampled input)
+        unf_f = bool(nfold) and has(2)
+        unf_b = bool(nfold) and has(3)
+        # THIS call's forward and input-gradient passes both run on prepared filters and read no weights (a list input, a
+        # misaligned operand or a geometry off the Winograd passes sends a strided layer to the implicit GEMM, which does)
+        raw_ok = (FILTERS_FROM_RAW and cmap is None and ((unf_f and unf_b) if nfold else (has(0) and has(1))) and
+                  all(t is None or t.data_ptr() % 16 == 0 for t in (x, V2d, b)))
+
+        def compute(raw=raw_ok):
+            if raw:
+                # the filters come from (V, g * inv_norm) and the normalised copies are never written.  `scale` takes their
+                # place in the entry (it carries w's record)
+                scale, inv_norm = weightnorm_scale(V2d, g)
+                return scale, scale, inv_norm, {"fwd": prepare_filters(desc, 2 if nfold else 0, scale), "bwd": None,
+                                                "bwd_done": False, "bwd_which": 3 if nfold else 1, "raw": scale}
             w, wT, inv_norm = weightnorm_fwd(V2d, g)
             wd = w                       # operand of dgrad
-            # Winograd passes of a folded layer take filters made from the UN-folded weights (which = 2 forward,
-            # 3 dgrad: no fold pass at all); a layer may have only the forward one (3x3 on an upsampled input)
-            unf_f = bool(nfold) and _lib.lib().otgan_conv2d_filter_bytes(ctypes.byref(desc), 2) > 0
-            unf_b = bool(nfold) and _lib.lib().otgan_conv2d_filter_bytes(ctypes.byref(desc), 3) > 0
             if nfold and not (unf_f and unf_b):
                 # conv o upsample == four parity-class convs with pre-summed taps (otgan_layers.h)
                 wd_f, wT_f = fold_weights(desc, w)
@@ -576,6 +622,10 @@ class Conv2dFunction(torch.autograd.Function):
                                       "bwd_done": False, "bwd_which": 3 if unf_b else 1}
 
         wd, wT, inv_norm, filt = cached_weights(V, g, compute)
+        if "raw" in filt and not raw_ok:
+            # the entry (keyed by the parameter alone) was made by a call whose passes read no weights; this one's may:
+            # it gets normalised weights of its own, and the entry stays for the calls it serves
+            wd, wT, inv_norm, filt = compute(False)
         # left by the weight-norm kernel (same values in w and wT); the implicit-GEMM passes' two-piece fp16 loop scales the
         # weights by it (else it reduces them itself)
         ctx.w_rec = amax_of(wT)
@@ -602,7 +652,9 @@ class Conv2dFunction(torch.autograd.Function):
             # gated product (and its amax record) too; GluFunction.forward picks it up instead of reading y again
             y_glu = torch.empty((N, OH, OW, Cout // 2), dtype=x.dtype, device=x.device)
             glu_rec = amax_slot(x.device)
-        conv_fwd_raw(fwd, x, cmap, wT, b, y, filt["fwd"], y_amax_out=y_rec, glu_out=y_glu, glu_amax_out=glu_rec)
+        # (an entry without normalised weights: with `filters` the pass reads none; V2d is a valid pointer of w's size)
+        conv_fwd_raw(fwd, x, cmap, V2d if "raw" in filt else wT, b, y, filt["fwd"], y_amax_out=y_rec, glu_out=y_glu,
+                     glu_amax_out=glu_rec)
         if y_glu is not None:
             leave(y, "glu", tag_amax(y_glu, glu_rec))
             _PENDING_GLU[0] = weakref.ref(y)
@@ -614,6 +666,10 @@ class Conv2dFunction(torch.autograd.Function):
             # side stream, under this forward pass, instead of on the backward pass's critical path
             cur = torch.cuda.current_stream()
             SIDE_STREAM.wait_stream(cur)                 # (the normalised weights were written on this stream)
+            # (an entry without normalised weights: this launch reads the PARAMETER V on the side stream, not a snapshot.
+            # Whoever writes V next must have joined the side stream: the backward pass waits for bwd_event, and a step joins
+            # before its optimiser runs (join_side_stream).  A caller that runs forward passes only under grad mode and then
+            # updates V through raw pointers has to join as well.)
             with torch.cuda.stream(SIDE_STREAM):
                 filt["bwd"], filt["bwd_done"] = prepare_filters(desc, filt["bwd_which"], wd), True
                 filt["bwd_event"] = SIDE_STREAM.record_event()
@@ -633,6 +689,9 @@ class Conv2dFunction(torch.autograd.Function):
         ld = channel_prefix_stride(dy)
         if ld is None:
             dy = carry_amax(dy.contiguous(), dy)
+            if "raw" in ctx.filt and dy.data_ptr() % 16:
+                # (a misaligned dy would send a strided layer's input gradient off the Winograd pass, to one that reads weights)
+                dy = carry_amax(dy.clone(), dy)
             ld = dy.shape[-1]
         dx = dV = dg = db = None
         dy_rec = None
@@ -647,8 +706,14 @@ class Conv2dFunction(torch.autograd.Function):
         if ctx.needs_input_grad[0]:
             dx = torch.empty_like(x)
             filt = ctx.filt
+            if "raw" in filt:
+                # no normalised weights in this entry: the filters come from (V, scale) -- also the ones a later step makes on a
+                # cache hit -- and the pass, which reads none with `filters`, gets V2d as its weight pointer
+                src, w = filt["raw"], V2d
+            else:
+                src = w
             if not filt["bwd_done"]:
-                filt["bwd"], filt["bwd_done"] = prepare_filters(desc, filt["bwd_which"], w), True
+                filt["bwd"], filt["bwd_done"] = prepare_filters(desc, filt["bwd_which"], src), True
             elif filt.get("bwd_event") is not None:
                 # made on the side stream during a forward pass: this stream waits for that launch (once is enough, but the
                 # wait is free when the event has long completed) and the buffer is in use here from now on
