@@ -519,6 +519,32 @@ int otgan_knn_f64(int nq, int ny, int C, const float* q, int ldq, const float* y
                   void* stream);
 
 /*
+ * Nearest neighbours BY IDENTITY, for the k-NN probe of the critic's features (utils/probe.py), fp64 MFMA, the Gram
+ * matrix never written.  With s(a, b) = a . b, for every query row i < nq over the columns j < ny with j != self0 + i
+ * (self0 = -1: no column is excluded, as in otgan_knn_f64):
+ *   index[i][0 .. k) = the columns of the k largest s(q_i, y_j),
+ *   score[i][0 .. k) = those values (score may be null),
+ * sorted by score descending, equal scores by the SMALLER COLUMN first: a total order, so the outputs are a function of
+ * the inputs alone -- not of the order in which columns are visited, of a row's place in the call or of how the columns
+ * are split over workgroups; no atomics.  Slots beyond the number of counted columns hold index -1 and score -inf; a
+ * counted column, however negative its score, is never displaced by one.
+ * q, y: fp32 rows of C channels with row strides ldq, ldy >= C, 16-byte aligned with strides that are multiples of 4,
+ * C % 4 == 0 (the rules of otgan_knn_f64); index: int32 [nq][k]; score: double [nq][k]; both OVERWRITTEN.  1 <= k <= 8.
+ * The exclusion is by POSITION: another row with the same values is returned, with the score s(a, a).  The fp32 inputs
+ * are converted to fp64 before the multiply, and every dot product adds its channels in the order of the one loop that
+ * otgan_knn_f64 and otgan_kid_sums_f64 run, which depends on C only: s(a, b) and s(b, a) are the same bits in any
+ * call, tile or operand role.  workspace: otgan_topk_dot_workspace_bytes(nq, ny, k) bytes, 8-byte aligned -- k doubles
+ * and k int32 per (column split, query row); OTGAN_ERR_WORKSPACE when smaller.  nq == 0 returns OTGAN_OK; ny == 0 fills
+ * every slot with -1 and -inf (no workspace needed).  An argument error returns nonzero without touching the outputs.
+ * The inputs must be FINITE: a NaN score (a NaN or infinite input row) compares false with everything, so such a column is
+ * never listed and its row may report fewer than k neighbours; nothing checks for it.  Column numbers are int32 with
+ * 2^31 - 1 reserved for an empty slot, which ny as an int can never reach.
+ */
+size_t otgan_topk_dot_workspace_bytes(int nq, int ny, int k);
+int otgan_topk_dot_f64(int nq, int ny, int C, const float* q, int ldq, const float* y, int ldy, int k, int self0,
+                       int32_t* index, double* score, void* workspace, size_t workspace_bytes, void* stream);
+
+/*
  * The training batch from a device-resident uint8 dataset in ONE launch (csrc/data.hip; utils/data.py): gather by the
  * epoch's permutation, per-image horizontal flip, uint8 -> [-1, 1] and an optional integer box-downsample -- what the
  * reference does on the host per step (train.py:158,163-170,209-211).

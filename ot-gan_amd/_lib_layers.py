@@ -129,6 +129,8 @@ SIGNATURES = {
     "otgan_kid_sums_f64": (c_int, [c_int, c_int, c_int, c_fp, c_int, c_fp, c_fp, c_int, c_fp, c_fp, c_fp, c_size_t, c_fp]),
     "otgan_knn_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
     "otgan_knn_f64": (c_int, [c_int, c_int, c_int, c_fp, c_int, c_fp, c_int, c_int, c_int, c_fp, c_fp, c_fp, c_fp, c_size_t, c_fp]),
+    "otgan_topk_dot_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "otgan_topk_dot_f64": (c_int, [c_int, c_int, c_int, c_fp, c_int, c_fp, c_int, c_int, c_int, c_fp, c_fp, c_fp, c_size_t, c_fp]),
     "otgan_batch_from_u8_f32": (c_int, [c_fp, c_long, c_int, c_int, c_fp, c_long, c_fp, c_int, c_int, c_fp, c_fp, c_int,
                                         c_fp, c_long, c_fp]),
 }

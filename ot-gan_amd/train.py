@@ -16,6 +16,9 @@ train.py:245-272: --inception_model takes the reference's own 2015 graph file, o
 --fid_stats / --fid_real_samples (the Frechet Inception Distance beside every score, utils/fid.py),
 --kid_subsets / --kid_subset_size / --kid_real_samples (the Kernel Inception Distance beside them, utils/kid.py),
 --pr_neighbours / --pr_real_samples (precision, recall, density and coverage beside them, utils/pr.py),
+--probe_every / --probe_neighbours / --probe_train_samples / --probe_test_samples (the critic's score: k-NN classification of
+held-out labelled images in the critic's own features, utils/probe.py -- the measurement the reference loads its labels and
+test set for, train.py:199, and leaves empty),
 --dataset cifar10|imagenet64|npy and --data_on_device (utils/data.py): the training set lives on the device as uint8 and
 one kernel launch per step gathers, flips and converts the step's batch; 64 x 64 data (the downsampled-ImageNet pickles, a
 .npy of one's own images) comes in this way only.  Guarantee: `--dataset cifar10 --data_on_device` feeds `model.step` the
@@ -100,6 +103,15 @@ def build_parser():
     p.add_argument('--pr_real_samples', type=int, default=0,
                    help='training images behind the real side of precision and recall: the first N (0 = min(eval_samples, '
                         'training images))')
+    p.add_argument('--probe_every', type=int, default=0,
+                   help="score the critic's features every this many epochs by k-NN classification of held-out labelled images "
+                        "against training images in the critic's own cosine geometry (utils/probe.py; the reference's comment "
+                        "says 50, train.py:199).  Needs a dataset with labels; 0 = off")
+    p.add_argument('--probe_neighbours', type=int, default=5, help='neighbours that vote in the probe (1 ... 8)')
+    p.add_argument('--probe_train_samples', type=int, default=5000, help='training images the probe searches: the first N')
+    p.add_argument('--probe_test_samples', type=int, default=1000,
+                   help='held-out images the probe classifies: the first N of test_batch / val_data (an .npz has no held-out '
+                        'subset: its training images are classified leave-one-out)')
     p.add_argument('--step_graph', type=int, nargs='?', const=1, default=None, choices=(0, 1),
                    help='replay whole steps as hipGraphs after the first period (single-process runs; bit-identical to the '
                         'eager steps).  Default: on for --model densenet (launch-bound: replay 25.5 ms against 27.6 - 29.6 ms), '
@@ -281,6 +293,79 @@ def real_pr_state(args, classifier, trainx, rank=0, world=1, kid_bank=None):
     return {"pr_real": made[0], "pr_real_radii": pr.radii(made[0].rows, made[1], rank, world)} if made else {}
 
 
+def probe_state(args, trainx, dev, rank=0, world=1):
+    """--probe_every: what the probe keeps for the run -- {"bank": the training set (the probe reads its first "n_bank"
+    images), "bank_labels" / "query_labels": int64 on the device, "queries": the first --probe_test_samples held-out images
+    as a uint8 device store (None: leave-one-out on the bank, an .npz has no held-out subset), "max" / "iter": the running
+    best}.  None, said once by rank 0, for data without labels and for --synthetic: the run trains as without the flag.
+    A bank with no more than K rows is a ValueError here, before the first step."""
+    from .utils import data as udata, probe
+    say = print if rank == 0 else (lambda *a: None)
+    if args.synthetic:
+        say('--probe_every: --synthetic data has no labels; the critic k-NN probe is skipped')
+        return None
+    labels = udata.load_labels(args.dataset, args.data_dir)
+    if labels is None:
+        say('--probe_every: %s carries no labels; the critic k-NN probe is skipped' % args.data_dir)
+        return None
+    n_bank = min(args.probe_train_samples, trainx.shape[0])
+    probe.check_neighbours(args.probe_neighbours, n_bank)
+    state = {"bank": trainx, "n_bank": n_bank, "bank_labels": torch.from_numpy(labels[:n_bank]).to(dev), "queries": None,
+             "query_labels": None, "max": -1.0, "iter": 0}
+    if args.dataset == 'npy':
+        say('--probe_every: an .npz has no held-out subset; the first %d training images are classified leave-one-out' % n_bank)
+        return state
+    held_labels = udata.load_labels(args.dataset, args.data_dir, 'test')
+    if held_labels is None:
+        say('--probe_every: the held-out subset under %s carries no labels; the critic k-NN probe is skipped' % args.data_dir)
+        return None
+    held = udata.load_u8(args.dataset, args.data_dir, 'test')[:max(args.probe_test_samples, 0)]
+    if held.shape[0] == 0:
+        raise ValueError("--probe_test_samples %d: the probe needs at least one held-out image" % args.probe_test_samples)
+    state["queries"] = udata.DeviceDataset(held, dev, args.image_size)
+    state["query_labels"] = torch.from_numpy(held_labels[:held.shape[0]]).to(dev)
+    return state
+
+
+def probe_hook(model, args, state, rank=0, world=1):
+    """The critic's score (utils/probe.py): k-NN classification of the held-out images against the first training images in
+    the critic's features of this moment.  Every rank takes part: it runs the critic over its share of both sets
+    (OTGAN.critic_features, in batches of at most OTGAN.PROBE_BATCH rows of its share, unflipped, in storage order), the
+    bank is gathered and the counts are summed; rank 0 prints.  Training is untouched: no random draw, no parameter
+    written."""
+    from .utils import features, probe
+
+    def feats(images, lo, hi):
+        out = [torch.empty(0, model.num_features, device=model.device)]
+        for i in range(lo, hi, model.PROBE_BATCH):
+            j = min(i + model.PROBE_BATCH, hi)
+            if hasattr(images, "rows"):
+                x = images.rows(i, j)
+            else:
+                x = torch.from_numpy(np.ascontiguousarray(images[i:j], np.float32)).to(model.device)
+            out.append(model.critic_features(x))
+        return torch.cat(out)
+
+    k = args.probe_neighbours
+    lo, hi = features.share(state["n_bank"], rank, world)
+    bank, bank_labels = feats(state["bank"], lo, hi), state["bank_labels"][lo:hi]
+    if state["queries"] is None:
+        right_k, right_1, n = probe.accuracy(bank, bank_labels, None, None, k, rank, world, leave_one_out=True)
+    else:
+        qlo, qhi = features.share(state["queries"].shape[0], rank, world)
+        right_k, right_1, n = probe.accuracy(bank, bank_labels, feats(state["queries"], qlo, qhi),
+                                             state["query_labels"][qlo:qhi], k, rank, world)
+    acc = right_k / n
+    if rank == 0:
+        print('critic k-NN accuracy was %.4f (K = %d), 1-NN was %.4f, %d held-out against %d training images'
+              % (acc, k, right_1 / n, n, state["n_bank"]))
+    if acc > state["max"]:
+        state["max"], state["iter"] = acc, state["epoch"]
+        if rank == 0:
+            print('max critic k-NN accuracy was %.4f, iter was %d' % (state["max"], state["iter"]))
+    return acc, right_1 / n
+
+
 def load_cifar(data_dir, subset='train'):
     """Pickled CIFAR-10 python batches under <data_dir>/cifar-10-python/cifar-10-batches-py
     (the layout the reference's data/cifar10_data.py:40-53 reads; no download here)."""
@@ -332,6 +417,11 @@ def main(argv=None, self_launch=False):
     own process unless it passes --ranks explicitly -- never a surprise SystemExit."""
     args = build_parser().parse_args(argv)
     assert args.nr_gpu % 2 == 0                                   # train.py:34
+    from .utils import probe
+    try:
+        probe.check_neighbours(args.probe_neighbours)
+    except ValueError as e:
+        raise ValueError("--probe_neighbours: %s" % e) from None
     from . import parallel
     from .trainer import OTGAN
     if not parallel.launched() and (self_launch or args.ranks):
@@ -399,6 +489,7 @@ def main(argv=None, self_launch=False):
         score_state.update(real_kid_state(args, classifier, trainx, rank, world))
     if args.pr_neighbours > 0:
         score_state.update(real_pr_state(args, classifier, trainx, rank, world, score_state.get("kid_real")))
+    probe_st = probe_state(args, trainx, dev, rank, world) if args.probe_every > 0 else None
     start_time = time.time()
     total = 0
     for epoch in range(current_epoch, 1000000):
@@ -434,6 +525,9 @@ def main(argv=None, self_launch=False):
         if classifier is not None and (epoch + 1) % args.eval_every == 0 and epoch != current_epoch:   # train.py:245
             score_state["epoch"] = epoch
             inception_hook(model, args, classifier, score_state, rank, world)
+        if probe_st is not None and (epoch + 1) % args.probe_every == 0 and epoch != current_epoch:
+            probe_st["epoch"] = epoch
+            probe_hook(model, args, probe_st, rank, world)
         if rank == 0:
             print("Iteration %d, time = %ds, train distance before gen = %.6f, train distance before disc = %.6f, "
                   "avg matching entropy = %.6f" % (epoch, time.time() - begin, mean_dist_gen[-1],

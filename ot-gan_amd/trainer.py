@@ -449,6 +449,25 @@ class OTGAN:
     def sample(self, n, ema=False):
         return self.generator(batch_size=n, ema=self.ema if ema else None, device=self.device, **self.model_opts)
 
+    PROBE_BATCH = 500       # rows per critic forward of the k-NN probe (train.probe_hook)
+
+    @torch.no_grad()
+    def critic_features(self, x):
+        """[n, num_features] fp32: the critic's unit-norm features of the batch x ([n, H, W, 3] in [-1, 1]), unflipped, outside
+        any step (utils/probe.py scores them by k-NN classification).  The activation scales of the convolution kernels
+        depend on the content of the batch, so a row's features are defined together with its batch: the probe calls this
+        in fixed batches of min(PROBE_BATCH, rows left), in storage order, and that batching is part of the number's
+        definition.  Draws from no random stream and changes no training state.  With step graphs (GraphedSteps) the pass
+        meets the critic's cached operands in one of two states: valid -- it reads them, which changes nothing, and while
+        `_d_weights_in_graph` holds the "gen1" graph's entries are put back afterwards, so that a "gen" or "disc" capture
+        can only ever read those; or invalid, after a critic step -- it refills them, and the next step is "gen1", whose
+        capture invalidates them and whose replay reinstates its own (tests/test_probe_gpu.py::test_training_unchanged)."""
+        from . import ops
+        f = self.discriminator(x, **self.model_opts).float()
+        if self.graphs is not None and self._d_weights_in_graph and self.graphs.critic_ops is not None:
+            ops.reinstate_weights(self.graphs.critic_ops)
+        return f
+
     # ---------------------------------------------------------------- checkpoint (train.py:60,190-193,275-277)
     def state_dict(self, full=True):
         """Variables under the reference's names ('discriminator/conv2d_0/V', ...) + the step counter --
@@ -801,7 +820,8 @@ def default_args(**over):
              synthetic_size=50000, data_dependent_init=False, eval_every=100, eval_samples=50000,
              inception_model='', ranks=0, step_graph=None, fid_stats='', fid_real_samples=0, dataset='cifar10',
              data_on_device=False, kid_subsets=0, kid_subset_size=1000, kid_real_samples=0,
-             pr_neighbours=0, pr_real_samples=0)
+             pr_neighbours=0, pr_real_samples=0, probe_every=0, probe_neighbours=5, probe_train_samples=5000,
+             probe_test_samples=1000)
     d.update(over)
     return argparse.Namespace(**d)
 

@@ -8,6 +8,8 @@ integer box-downsample by 2 or 4 when the stored images are larger than the mode
 
     load_u8(dataset, data_dir, subset)     -> uint8 [n, H, W, 3] (numpy; a memory map for .npy files)
     DeviceDataset(u8, device, image_size)  -> the store, the conversion table and the epoch's permutation on the device
+    load_labels(dataset, data_dir, subset) -> int64 [n] class labels of the same images, or None (utils/probe.py; never fed
+                                              to training)
 
 The table is `np.arange(256, dtype=np.float32) / 127.5 - 1.`, the expression train.load_cifar applies to the same bytes,
 so at equal sizes the device path returns the host path's bits.
@@ -98,6 +100,66 @@ def load_u8(dataset, data_dir, subset="train"):
         else:
             a = np.load(data_dir, mmap_mode="r")
         return _check_u8_images(a, data_dir)
+    raise ValueError("--dataset %r: one of %s" % (dataset, ", ".join(DATASETS)))
+
+
+def load_labels(dataset, data_dir, subset="train"):
+    """int64 [n]: the class labels of the images `load_u8(dataset, data_dir, subset)` returns, in its order, or None when
+    the files carry none (utils/probe.py scores features by them; training never reads them).
+
+    cifar10     key `labels` of data_batch_1 ... 5 | test_batch
+    imagenet64  key `labels` of the train batches that are there | val_data, as stored
+    npy         key `labels` of an .npz; a bare .npy has none
+    The row count must equal the image count of the same subset: a ValueError names both otherwise."""
+    def checked(labels, images, where):
+        labels = np.asarray(labels).reshape(-1).astype(np.int64)
+        if labels.shape[0] != images:
+            raise ValueError("%s: %d labels for %d images" % (where, labels.shape[0], images))
+        return labels
+
+    if dataset == "cifar10":
+        d = os.path.join(data_dir, "cifar-10-python", "cifar-10-batches-py")
+        files = ["data_batch_%d" % i for i in range(1, 6)] if subset == "train" else ["test_batch"]
+        labels, images = [], 0
+        for f in files:
+            with open(os.path.join(d, f), "rb") as fo:
+                e = pickle.load(fo, encoding="latin1")
+            if "labels" not in e:
+                return None
+            labels.append(np.asarray(e["labels"]).reshape(-1))
+            images += np.asarray(e["data"]).shape[0]
+        return checked(np.concatenate(labels), images, d)
+    if dataset == "imagenet64":
+        files = ["train_data_batch_%d" % i for i in range(1, 11)] if subset == "train" else ["val_data"]
+        labels, images = [], 0
+        for f in files:
+            path = os.path.join(data_dir, f)          # each file is opened once: a train batch is 1.2 GB unpickled
+            if os.path.exists(path):
+                with open(path, "rb") as fo:
+                    e = pickle.load(fo, encoding="latin1")
+                got, n = e.get("labels"), np.asarray(e["data"]).shape[0]
+            elif os.path.exists(path + ".npz"):
+                with np.load(path + ".npz") as e:
+                    got, n = (e["labels"] if "labels" in e.files else None), e["data"].shape[0]
+            else:
+                continue
+            if got is None:
+                return None
+            labels.append(np.asarray(got).reshape(-1))
+            images += n
+        if not labels:
+            raise FileNotFoundError("no %s (pickle or .npz) under %s" % (" ... ".join(files[::max(len(files) - 1, 1)]), data_dir))
+        return checked(np.concatenate(labels), images, data_dir)
+    if dataset == "npy":
+        if not data_dir.endswith(".npz"):
+            return None
+        with np.load(data_dir) as f:
+            if "labels" not in f.files:
+                return None
+            keys = [k for k in ("images", "data") if k in f.files]
+            if not keys:
+                raise ValueError("%s: no key `images` or `data` (it holds %s)" % (data_dir, ", ".join(f.files) or "nothing"))
+            return checked(f["labels"], f[keys[0]].shape[0], data_dir)
     raise ValueError("--dataset %r: one of %s" % (dataset, ", ".join(DATASETS)))
 
 
