@@ -567,4 +567,41 @@ int otgan_batch_from_u8_f32(const uint8_t* store, long n_images, int SH, int SW,
                             const long* shard_offsets, int n_shards, int B, const uint8_t* flip, const float* lut, int S,
                             float* out, long ldo, void* stream);
 
+/*
+ * Differentiable augmentation of the critic's inputs (Zhao et al. 2020, "DiffAugment"; csrc/augment.hip, utils/augment.py):
+ * y = T(x) per image, T = cutout o translation o colour with parameters derived ON THE DEVICE from the image's row of
+ * uniforms, and dx = T^T dy, the exact transpose (T is affine in x: the brightness offset has no transpose term).
+ *   x, y, dy, dx: fp32 NHWC [rows][S][S][3], contiguous, 16-byte aligned, output distinct from input; S % 4 == 0, 4 <= S <= 64.
+ *   u: device fp32 [rows][8], uniforms in [0, 1); slot 7 is unused.
+ *   policy: OTGAN_AUG_COLOR | OTGAN_AUG_TRANSLATION | OTGAN_AUG_CUTOUT; a group whose bit is off is the identity and its slots
+ *   are not read as parameters.  Policy 0 is a plain copy.
+ * Parameters of image r from u[r] (fp32 arithmetic, every float -> int by truncation):
+ *   colour:       b = u0 - 0.5f,  ks = 2 u1,  kc = u2 + 0.5f
+ *   translation:  R = (S + 4) / 8 (4 at 32, 8 at 64);  tx = min((int)(u3 (2R + 1)), 2R) - R,  ty likewise from u4
+ *   cutout:       c = S / 2;  ox = min((int)(u5 (S + 1)), S),  oy likewise from u6;  the window is
+ *                 [ox - c/2, ox + c/2) x [oy - c/2, oy + c/2) (columns x rows) intersected with the image
+ * Forward, output pixel (yy, xx), channel ch:
+ *   +0.0f                              if (yy, xx) lies in the cutout window,
+ *   +0.0f                              else if the source pixel (yy - ty, xx - tx) is outside the image,
+ *   colour(x[r][yy - ty][xx - tx])[ch] else, where for a pixel v = (v_R, v_G, v_B)
+ *     v1 = v + b;   m = (v1_R + v1_G + v1_B) / 3;   v2 = (v1 - m) ks + m;
+ *     mu = (sum of all 3 S^2 elements of x[r]) / (3 S^2) + b;   v3 = (v2 - mu) kc + mu = colour(v).
+ *   Without OTGAN_AUG_COLOR colour() is not evaluated: a copied element has the bits of its source.
+ * Backward:
+ *   e[q]  = dy[q + t] where the output position q + t = (y + ty, x + tx) is inside the image and outside the window, else 0;
+ *   e2    = kc e + (1 - kc) mean_image(e)            (mean over the 3 S^2 elements of the image)
+ *   dx    = ks e2 + (1 - ks) mean_channels(e2)       (mean over the 3 channels of the pixel);   dx = e without OTGAN_AUG_COLOR.
+ * Deterministic and position-independent: one workgroup per image; both per-image sums run in a fixed order that depends on S
+ * only (a fixed sequence per thread, a wave butterfly, a fixed tree over the waves; no atomics, nothing crosses a workgroup),
+ * so an image's output bits depend on its pixels, its row of u, S and policy -- not on rows, its row index or the call.
+ * Each entry point enqueues exactly one kernel on `stream` (none for rows == 0): no allocation, no copy, no synchronisation.
+ * A null pointer, rows < 0, an unsupported S, a policy outside the mask or a misaligned pointer returns OTGAN_ERR_INVALID
+ * with a message before any launch.
+ */
+#define OTGAN_AUG_COLOR 1
+#define OTGAN_AUG_TRANSLATION 2
+#define OTGAN_AUG_CUTOUT 4
+int otgan_augment_fwd_f32(const float* x, long rows, int S, const float* u, int policy, float* y, void* stream);
+int otgan_augment_bwd_f32(const float* dy, long rows, int S, const float* u, int policy, float* dx, void* stream);
+
 #endif /* OTGAN_LAYERS_H */

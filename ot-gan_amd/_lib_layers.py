@@ -133,4 +133,6 @@ SIGNATURES = {
     "otgan_topk_dot_f64": (c_int, [c_int, c_int, c_int, c_fp, c_int, c_fp, c_int, c_int, c_int, c_fp, c_fp, c_fp, c_size_t, c_fp]),
     "otgan_batch_from_u8_f32": (c_int, [c_fp, c_long, c_int, c_int, c_fp, c_long, c_fp, c_int, c_int, c_fp, c_fp, c_int,
                                         c_fp, c_long, c_fp]),
+    "otgan_augment_fwd_f32": (c_int, [c_fp, c_long, c_int, c_fp, c_int, c_fp, c_fp]),
+    "otgan_augment_bwd_f32": (c_int, [c_fp, c_long, c_int, c_fp, c_int, c_fp, c_fp]),
 }

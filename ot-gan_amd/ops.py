@@ -1871,3 +1871,51 @@ def batch_from_u8(store, offsets, B, S, lut, perm=None, flip=None, out=None):
                                                       lut.data_ptr(), int(S), out.data_ptr(), out.stride(0) if rows > 1 else 3 * S * S,
                                                       _lib.stream_ptr()), "batch_from_u8")
     return out
+
+
+AUG_COLOR, AUG_TRANSLATION, AUG_CUTOUT = 1, 2, 4      # include/otgan_layers.h: OTGAN_AUG_*
+
+
+def _augment_launch(fn, name, src, u, policy):
+    """One launch of otgan_augment_{fwd,bwd}_f32 on the current stream: src [rows, S, S, 3] fp32 -> a new tensor of its shape."""
+    _need_cuda(src, u)
+    src = src.contiguous()
+    if not (src.dtype == torch.float32 and src.dim() == 4 and src.shape[1] == src.shape[2] and src.shape[3] == 3):
+        raise _lib.OtganError("%s takes float32 [rows, S, S, 3] images, found %s %s" % (name, src.dtype, tuple(src.shape)))
+    rows, S = src.shape[0], src.shape[1]
+    if not (u.dtype == torch.float32 and tuple(u.shape) == (rows, 8) and u.is_contiguous() and u.device == src.device):
+        raise _lib.OtganError("%s: u must be contiguous float32 [%d, 8] on %s, found %s %s on %s"
+                              % (name, rows, src.device, u.dtype, tuple(u.shape), u.device))
+    out = torch.empty_like(src)
+    with torch.cuda.device(src.device):
+        _lib.check(fn(src.data_ptr(), rows, S, u.data_ptr(), int(policy), out.data_ptr(), _lib.stream_ptr()), name)
+    return out
+
+
+class AugmentFunction(torch.autograd.Function):
+    """y = T(x): colour / translation / cutout per image from its row of uniforms `u` (otgan_augment_fwd_f32; the formulas are
+    in include/otgan_layers.h), dx = T^T dy (otgan_augment_bwd_f32).  T is affine in x, so the backward pass needs u and the
+    policy only.  The output carries no amax record: its consumer reduces it, as it does the data batch."""
+
+    @staticmethod
+    def forward(ctx, x, u, policy):
+        ctx.policy = int(policy)
+        ctx.save_for_backward(u)
+        return _augment_launch(_lib.lib().otgan_augment_fwd_f32, "augment_fwd", x, u, policy)
+
+    @staticmethod
+    def backward(ctx, dy):
+        (u,) = ctx.saved_tensors
+        return augment_transpose(dy, u, ctx.policy), None, None
+
+
+def augment(x, u, policy):
+    """T(x) for a batch x [rows, S, S, 3] in fp32, u [rows, 8] uniforms in [0, 1), policy a mask of AUG_COLOR | AUG_TRANSLATION
+    | AUG_CUTOUT (utils/augment.parse_policy).  One launch; the backward launch exists only where x needs a gradient (autograd
+    builds no node otherwise: the critic step never runs it)."""
+    return AugmentFunction.apply(x, u, policy)
+
+
+def augment_transpose(dy, u, policy):
+    """T^T dy: the backward launch of `augment` on its own (no autograd)."""
+    return _augment_launch(_lib.lib().otgan_augment_bwd_f32, "augment_bwd", dy, u, policy)

@@ -22,7 +22,11 @@ test set for, train.py:199, and leaves empty),
 --dataset cifar10|imagenet64|npy and --data_on_device (utils/data.py): the training set lives on the device as uint8 and
 one kernel launch per step gathers, flips and converts the step's batch; 64 x 64 data (the downsampled-ImageNet pickles, a
 .npy of one's own images) comes in this way only.  Guarantee: `--dataset cifar10 --data_on_device` feeds `model.step` the
-same bits as the default host path, step for step (same host and device random streams, same conversion table).
+same bits as the default host path, step for step (same host and device random streams, same conversion table),
+--augment color,translation,cutout (utils/augment.py, ops.augment: differentiable augmentation, Zhao et al. 2020 -- one random
+colour / translation / cutout transform per image in front of every critic pass of a training step, real and generated, with
+the generator's gradient taken through it; the lever against a critic that memorises a small training set.  Samples, metrics,
+the probe and the initialisation pass are never augmented; '' = off, and the step is then the reference's bit for bit).
 
 Checkpoints (`<save_dir>/med_gan_params-<epoch>`, the reference's naming, train.py:275-277) are torch pickles
 of {variable name: tensor} plus optimiser moments / step count and EMA shadows (which the reference's
@@ -124,6 +128,11 @@ def build_parser():
                    help='keep the training set on the device as uint8 and make every batch there in one launch (gather, flip, '
                         'uint8 -> [-1, 1]) instead of the per-step host gather and copy; the same batches bit for bit.  Implied by '
                         '--dataset imagenet64 | npy, which have no host-float path; with --synthetic: a random uint8 set')
+    p.add_argument('--augment', type=str, default='',
+                   help="differentiable augmentation of everything the critic sees in a training step (DiffAugment, Zhao et al. "
+                        "2020): a comma-separated subset of color,translation,cutout in any order, e.g. "
+                        "'color,translation,cutout'; the generator's gradient flows through the transform.  For small training "
+                        "sets.  '' = off (the reference's step)")
     return p
 
 
@@ -422,6 +431,11 @@ def main(argv=None, self_launch=False):
         probe.check_neighbours(args.probe_neighbours)
     except ValueError as e:
         raise ValueError("--probe_neighbours: %s" % e) from None
+    from .utils import augment
+    try:
+        policy = augment.parse_policy(args.augment)
+    except ValueError as e:
+        raise ValueError("--augment: %s" % e) from None
     from . import parallel
     from .trainer import OTGAN
     if not parallel.launched() and (self_launch or args.ranks):
@@ -464,6 +478,7 @@ def main(argv=None, self_launch=False):
     model = OTGAN(args, dev, init_batch=init_batch)
     if rank == 0:
         print("model has a hidden representation with %d features" % model.num_features)   # train.py:56
+        print("augmentation of the critic's inputs: %s (policy %d)" % (",".join(augment.policy_names(policy)) or "off", policy))
 
     per_step = args.nr_gpu * args.batch_size
     nr_batches = trainx.shape[0] // per_step                        # train.py:159

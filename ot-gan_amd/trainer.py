@@ -7,7 +7,7 @@ import os
 import torch
 
 from . import parallel
-from .utils import matching, nn
+from .utils import augment, matching, nn
 
 
 def _lib_prof_on():
@@ -89,6 +89,10 @@ class OTGAN:
         if self.scope == "local" and self.shards % 2 != 0:
             raise ValueError("local matching needs an even number of shards per rank")
         self.nb = self.shards * args.batch_size             # images per rank per step
+        # --augment: the same random colour / translation / cutout transform T in front of EVERY critic pass of a training
+        # step, real and generated, with the generator's gradient taken through T (DiffAugment; ops.augment).  0 = off: the
+        # step draws nothing and inserts nothing.
+        self.aug_policy = augment.parse_policy(getattr(args, "augment", ""))
         mod = importlib.import_module(f".models.{args.model}", package=__package__)  # train.py:38-41
         self.generator, self.discriminator = mod.generator, mod.discriminator
         self.generator.reset(seed=args.seed, device=device)
@@ -292,11 +296,12 @@ class OTGAN:
         return assemble_single_log_kernels(allk, self.args.sinkhorn_lambda)
 
     # ---------------------------------------------------------------- one sess.run
-    def step(self, x_data, noise=None, apply_updates=True):
+    def step(self, x_data, noise=None, aug=None, apply_updates=True):
         """x_data: [shards*batch_size, H, W, 3] in [-1, 1].  Runs a critic step when
         step_counter % (nr_gen_per_disc+1) == 0, else a generator step (train.py:214-226).
-        `noise` (tests) replaces the generator's own latent draw; `apply_updates=False`
-        (tests) leaves the parameters untouched and returns the summed gradients.
+        `noise` (tests) replaces the generator's own latent draw; `aug` (tests; with --augment) the step's
+        [2 * nb, 8] augmentation uniforms, rows [0, nb) for the real batch and [nb, 2 nb) for the generated one;
+        `apply_updates=False` (tests) leaves the parameters untouched and returns the summed gradients.
 
         With step graphs (single-process runs; default for densenet) the step is captured in a hipGraph per step kind after one
         eager period and replayed (GraphedSteps below): the same launches with the same arguments."""
@@ -305,7 +310,7 @@ class OTGAN:
         phase = self.step_counter % period
         kind = "disc" if phase == 0 else "gen"
         self._throttle()
-        if self.graphs is not None and noise is None and apply_updates:
+        if self.graphs is not None and noise is None and aug is None and apply_updates:
             done = self.graphs.run(x_data, phase)
             if done is not None:
                 self.last = done
@@ -314,7 +319,7 @@ class OTGAN:
         from . import ops
         ops.SIDE_STREAM = self._side_stream if self.fork_wgrad else None
         try:
-            dist, ent, grads = self._step_body(x_data, kind, noise, apply_updates)
+            dist, ent, grads = self._step_body(x_data, kind, noise, apply_updates, aug)
         finally:
             ops.SIDE_STREAM = None
         self._mark_step_end()
@@ -378,9 +383,18 @@ class OTGAN:
             n += 1
         return n
 
-    def _step_body(self, x_data, kind, noise=None, apply_updates=True):
+    def _step_body(self, x_data, kind, noise=None, apply_updates=True, aug=None):
         """The launches of one step (no host-side bookkeeping): -> (distance, entropy, summed gradients)."""
         a = self.args
+        T = None
+        if self.aug_policy:
+            # one draw per step, here on the main stream (a captured step records it like the generator's latent; the second
+            # stream waits for the main stream before it reads its rows): rows [0, nb) real, [nb, 2 nb) generated
+            from . import ops
+            u = aug if aug is not None else augment.draw(2 * self.nb, self.device)
+            assert tuple(u.shape) == (2 * self.nb, augment.SLOTS), "aug: [2 * nb, 8] uniforms"
+            T = lambda x, rows: ops.augment(x, u[rows], self.aug_policy)
+        real, fake, both = slice(0, self.nb), slice(self.nb, 2 * self.nb), slice(0, 2 * self.nb)
         gkw = dict(self.model_opts)
         if noise is not None:
             gkw["noise"] = noise
@@ -388,7 +402,8 @@ class OTGAN:
             with torch.no_grad():
                 ema = self.ema if a.train_disc_against_ema else None    # train.py:119-123
                 x_gen = self.generator(batch_size=self.nb, ema=ema, device=self.device, **gkw)
-            f_all = self.discriminator(torch.cat([x_data, x_gen], 0), **self.model_opts)
+            x_all = torch.cat([x_data, x_gen], 0)
+            f_all = self.discriminator(x_all if T is None else T(x_all, both), **self.model_opts)
             f_dat, f_gen = f_all[:self.nb], f_all[self.nb:]
             with self._timed("match_total"):
                 g_gen, g_dat, dist, ent = self._match(f_gen.detach(), f_dat.detach())
@@ -409,7 +424,7 @@ class OTGAN:
                 main = torch.cuda.current_stream()
                 side.wait_stream(main)
                 with torch.cuda.stream(side), torch.no_grad():
-                    f_dat = self.discriminator(x_data, **self.model_opts)
+                    f_dat = self.discriminator(x_data if T is None else T(x_data, real), **self.model_opts)
                     # overlapped schedule: the real features are final here -- their all-gather starts now, ordered behind
                     # the side stream, and runs under the generator's forward pass and the second critic pass
                     pending = None
@@ -421,7 +436,7 @@ class OTGAN:
                 main.wait_stream(side)
             else:
                 with torch.no_grad():
-                    f_dat = self.discriminator(x_data, **self.model_opts)
+                    f_dat = self.discriminator(x_data if T is None else T(x_data, real), **self.model_opts)
                 # the real-data features are final here: start their all-gather now, it overlaps the
                 # generator forward and the second critic pass
                 with self._timed("allgather_early"):
@@ -432,7 +447,7 @@ class OTGAN:
             # its variables frozen, so that its layers skip their weight gradients (autograd's needs_input_grad
             # follows requires_grad, not the `inputs` list of autograd.grad) and only propagate d/dx
             with _frozen(self.disc_params):
-                f_gen = self.discriminator(x_gen, **self.model_opts)
+                f_gen = self.discriminator(x_gen if T is None else T(x_gen, fake), **self.model_opts)
             with self._timed("match_total"):
                 g_gen, _g_dat, dist, ent = self._match(f_gen.detach(), f_dat, pending, need_dat=False)
             if self.gen_buckets is not None:
@@ -821,7 +836,7 @@ def default_args(**over):
              inception_model='', ranks=0, step_graph=None, fid_stats='', fid_real_samples=0, dataset='cifar10',
              data_on_device=False, kid_subsets=0, kid_subset_size=1000, kid_real_samples=0,
              pr_neighbours=0, pr_real_samples=0, probe_every=0, probe_neighbours=5, probe_train_samples=5000,
-             probe_test_samples=1000)
+             probe_test_samples=1000, augment='')
     d.update(over)
     return argparse.Namespace(**d)
 
