@@ -129,6 +129,14 @@ int otgan_matching_two_batch_rows_f32(const float* fa, const float* fb, int N, i
  * the Sinkhorn kernel's statistics (no pass over the features).  Cosine cost.  Workspace:
  * otgan_matching_grad_workspace_bytes.  The _rows_ variant produces rows [row_begin, +row_count) (inside one
  * mini-batch) into [row_count, D] buffers, K_pre as in otgan_matching_two_batch_rows_f32.
+ * Routes: any ldf >= D, ldo >= D, row_begin and row_count inside one mini-batch, and any alignment of the fp32 pointers, is
+ * accepted and gives the same values to the stated tolerance; only floats [0, D) of an output row are written.  The call runs
+ * on the split-precision engine when ALL of these hold, else on the exact-fp32 / one-tile fp16 kernels: N >= 256, N % 32 == 0,
+ * D % 32 == 0, D >= 64; ldf % 4 == 0 and fa, fb 16-byte aligned; ldo % 4 == 0 and grad_a, grad_b 16-byte aligned;
+ * row_begin % 32 == 0 (tests/matching_routes.py restates the predicates, tests/test_matching_routes_gpu.py runs every route).
+ * The single-batch entries below follow the same list with n for N; otgan_matching_two_batch_rows_f32 the same without the
+ * output-alignment term.  otgan_matching_two_batch_rows_grad_stack_f32 reads no fp32 features and REFUSES (OTGAN_ERR_INVALID)
+ * what the others fall back on.
  */
 size_t otgan_matching_grad_workspace_bytes(int N, int D);
 int otgan_matching_two_batch_grad_f32(const float* fa, const float* fb, int N, int D, long ldf,
@@ -155,7 +163,8 @@ int otgan_matching_two_batch_rows_grad_f32(const float* fa, const float* fb, int
  *                                   call (they share the operand's scale).
  *   otgan_cost_slices_stack_f32     K[p] = -lambda (1 - x.y) for P <= 6 problems: X = stack rows [xrow[p], +nrows),
  *                                   Y = the N-row block at stack row yrow[p] -> K [P][nrows][N].
- *   otgan_matching_two_batch_rows_grad_stack_f32   otgan_matching_two_batch_rows_grad_f32 reading the stack (K_pre required).
+ *   otgan_matching_two_batch_rows_grad_stack_f32   otgan_matching_two_batch_rows_grad_f32 reading the stack (K_pre required;
+ *                                   "Routes" there: a call off the engine's conditions is refused, not rerouted).
  */
 size_t otgan_matching_stack_bytes(int N, int D);
 int otgan_matching_stack_split_f32(const float* fa, const float* fb, int N, int D, long ldf, int nranges,
@@ -186,6 +195,7 @@ int otgan_matching_single_batch_f32(const float* fa, const float* fb, int n, int
  * data-parallel rank -- into [row_count, D] buffers; K_pre (nullable) = the three [n, n] log-kernels a-a, b-b (both with
  * -lambda*999 on the diagonal), a-b, e.g. assembled from the ranks' row slices (the reference shards exactly these
  * GEMMs over its towers, matching.py:99-104).  Workspace: otgan_matching_single_batch_grad_workspace_bytes.
+ * Pitches, row ranges, alignment and the engine's conditions: "Routes" at otgan_matching_two_batch_grad_f32.
  */
 size_t otgan_matching_single_batch_grad_workspace_bytes(int n, int D);
 int otgan_matching_single_batch_grad_f32(const float* fa, const float* fb, int n, int D, long ldf, float sinkhorn_lambda,

@@ -1591,6 +1591,12 @@ inline bool x3_shape_ok(int n, int m, int D) {
   return match_x3_enabled() && n >= 256 && m >= 256 && n % 32 == 0 && m % 32 == 0 && D % 32 == 0 && D >= 64;
 }
 
+// A row range on the engine's plan application (launch_apply_x3) starts on a PAIR of 16-column blocks of the t-leading plan
+// operand: a load fetches blocks (cb, cb + 1), and the clamp at the operand's last pair is to an even block, so a range that
+// started on an odd one and reached the last 16 rows of its half got the rows 16 in front of them (N = 256, rows [240, 256):
+// tests/test_matching_routes_gpu.py).  Such ranges run on the fp32 / one-tile kernels like every other shape the engine leaves.
+inline bool x3_row_begin_ok(int row_begin) { return row_begin % 32 == 0; }
+
 // K splits of the cost GEMM on the 256 x 256 engine: one workgroup per CU (a workgroup owns a CU's LDS), none
 // when there are enough tiles
 struct X3CostPlan {
@@ -2296,7 +2302,7 @@ int otgan_matching_two_batch_rows_f32(const float* fa, const float* fb, int N, i
   MatchCall c = {kTwoBatch, N, D, lambda, iters, (hipStream_t)stream};
   if ((rc = match_begin(c, false, workspace, workspace_bytes))) return rc;
   const int half = row_begin / N;      // rows of a1 / b1 (matching.py:64-67,72,74) or of a2 / b2 (:68-71,73,75)
-  const bool x3 = c.w.x3 && f.engine_ok() && ldo % 4 == 0 && row_begin % 16 == 0;
+  const bool x3 = c.w.x3 && f.engine_ok() && ldo % 4 == 0 && x3_row_begin_ok(row_begin);
   if (x3) x3_split_features(c.w, fa, fb, 2 * N, D, ldf, c.s);     // cost operand and B operand of the plan application
   rc = match_solve(c, x3, kStackArrays, f, K_pre);
   if (rc) return rc;
@@ -2328,7 +2334,7 @@ static int matching_grad_impl(const FeatSrc& f, int N, int D, float lambda, int 
   if ((rc = match_begin(c, true, workspace, workspace_bytes))) return rc;
   MatchWs& w = c.w;
   hipStream_t s = c.s;
-  const bool x3 = w.x3 && f.engine_ok() && ldo % 4 == 0 && aligned16(grad_a) && aligned16(grad_b) && row_begin % 16 == 0;
+  const bool x3 = w.x3 && f.engine_ok() && ldo % 4 == 0 && aligned16(grad_a) && aligned16(grad_b) && x3_row_begin_ok(row_begin);
   const StackLayout lay = kStackGrad.first(grad_b ? 6 : 4);
   if (f.stack) {
     // the caller split the blocks this call reads already (otgan_matching_stack_split_f32): same layout, its own buffer
@@ -2548,7 +2554,7 @@ static int single_grad_impl(const float* fa, const float* fb, int n, int D, long
   if ((rc = match_begin(c, true, workspace, workspace_bytes))) return rc;
   const MatchWs& w = c.w;
   hipStream_t s = c.s;
-  const bool x3 = w.x3 && f.engine_ok() && ldo % 4 == 0 && aligned16(grad_a) && aligned16(grad_b) && row_begin % 16 == 0;
+  const bool x3 = w.x3 && f.engine_ok() && ldo % 4 == 0 && aligned16(grad_a) && aligned16(grad_b) && x3_row_begin_ok(row_begin);
   if (x3) x3_split_features(w, fa, fb, n, D, ldf, s);
   rc = match_solve(c, x3, kStackSingle, f, K_pre);
   if (rc) return rc;
