@@ -50,7 +50,7 @@ typedef struct otgan_conv_desc {
   /* forward only: 1 = y += conv(x) + bias instead of y = ...  Implemented for the 3x3 / stride-1 / 16-output growth
    * layers (dense16 kernels) and for the wide 3x3 / stride-1 layers that take the Winograd path, which is what a dense
    * block split into "wide convolutions of finished channel groups + short growth chains" needs (ops.py
-   * DenseBlockFunction); any other layer with this flag set is rejected with OTGAN_ERR_ARG. */
+   * DenseBlockFunction); any other layer with this flag set is rejected with OTGAN_ERR_INVALID. */
   int y_accumulate;
   /* Optional: device buffer of otgan_conv2d_operand_bytes(d) bytes (16-byte aligned) shared by the forward call and the
    * weight-gradient call on the SAME x.  Both passes of a Winograd layer start with the same transform of x into the
@@ -58,7 +58,7 @@ typedef struct otgan_conv_desc {
    * and the weight-gradient call reads it instead of transforming x again (the buffer must stay untouched in
    * between; x_amax is then not needed by the weight gradient).  Ignored when otgan_conv2d_operand_bytes(d) == 0;
    * when it is > 0 and a call cannot take the Winograd path (list input, misaligned operands, short workspace) the
-   * call fails with OTGAN_ERR_ARG instead of silently writing / reading nothing.  NULL = each pass transforms x. */
+   * call fails with OTGAN_ERR_INVALID instead of silently writing / reading nothing.  NULL = each pass transforms x. */
   void* x_operand;
   /* Optional OUTPUT amax records (round 3): the kernel that WRITES y (forward) / dx (input gradient) also leaves the
    * largest |value| it wrote in the record -- atomically max-accumulated as the float's bit pattern, so the caller must
@@ -93,7 +93,7 @@ typedef struct otgan_conv_desc {
    * written, the backward pass of the unit needs it -- and, if glu_amax_out is non-NULL, max-accumulates the largest
    * |gated value| into that (zeroed) amax record.  Only where otgan_conv2d_glu_fused(d) returns 1 (the Winograd path of
    * the 5x5 upsampling layers, Cout % 8 == 0, y_coff == 0, ldy == Cout); any other layer with glu_out set is rejected
-   * with OTGAN_ERR_ARG.  Same arithmetic as otgan_glu_fwd_amax_f32 on y: bit-identical. */
+   * with OTGAN_ERR_INVALID.  Same arithmetic as otgan_glu_fwd_amax_f32 on y: bit-identical. */
   float* glu_out;
   float* glu_amax_out;
   /* (round 4) dy_amax points to this many consecutive records (see x_amax_count); 0 or 1 = one record. */
@@ -177,6 +177,23 @@ size_t otgan_conv2d_folded_weight_elems(const otgan_conv_desc* d);
 int otgan_conv2d_fold_weights_f32(const otgan_conv_desc* d, const float* w, float* weff,
                                   float* weffT, void* stream);
 
+/*
+ * The three passes below: what a pass does when a call does not meet the requirements of the layer's fast route (pinned by
+ * tests/test_conv_routes_gpu.py; pointers 16-byte aligned, pitches multiples of 4, a single-tensor input, a workspace of the
+ * size queried):
+ *   - 5x5 stride-2 and wide 3x3 stride-1 layers (Winograd): every pass falls back to the implicit GEMM, same result;
+ *     so do the 3x3 upsampling layers' weight gradient and, without `filters`, their forward / input gradient.
+ *   - folded 5x5 upsampling layers (Winograd) never fall back: misaligned operands / lddx % 4 != 0 are OTGAN_ERR_INVALID,
+ *     a NULL or short workspace is OTGAN_ERR_WORKSPACE.  3x3 upsampling layers called WITH `filters`: OTGAN_ERR_INVALID
+ *     for either (forward and input gradient).  Other folded layers need 16-byte aligned x and wT in the forward pass.
+ *   - input gradient through an un-folded 2x upsample, weight gradients that split their pixels, of folded layers and of
+ *     few-channel layers (Cout <= 4, or Cin_eff <= 4 without pre-activation): OTGAN_ERR_WORKSPACE on a NULL or short
+ *     workspace.  A weight gradient on float4 gathers (Cin_eff >= 32, everything a multiple of 4) needs 16-byte aligned x
+ *     and dy: OTGAN_ERR_INVALID otherwise.
+ *   - everything else (misaligned y / bias / dx / dw, odd pitches and channel counts, a NULL workspace elsewhere) only
+ *     selects slower kernels, which read and write nothing outside the rows the descriptor describes.  A refused call
+ *     writes nothing.
+ */
 /* y = conv2d(preact(upsample(x)), W) + bias.   wT: [Cout][KH*KW*Cin_eff] (transposed copy
  * of the HWIO weight, produced by otgan_weightnorm_fwd_f32).  nn.py:241,337. */
 int otgan_conv2d_fwd_f32(const otgan_conv_desc* d, const float* x, const int32_t* cmap,
@@ -203,8 +220,8 @@ int otgan_conv2d_dgrad_f32(const otgan_conv_desc* d, const float* dy, const floa
  *                                         with `filters` given they do not read their weight argument).
  *                                         3x3 layers on an upsampled CReLU input have ONLY these two (their
  *                                         forward / dgrad run as Winograd GEMMs exactly when `filters` is given;
- *                                         a dgrad call with `filters` must then satisfy that path's alignment /
- *                                         workspace requirements -- it is rejected otherwise, never rerouted)
+ *                                         a forward or dgrad call with `filters` must then satisfy that path's
+ *                                         alignment / workspace requirements -- it is rejected otherwise, never rerouted)
  *   otgan_conv2d_fwd_pf_f32 / otgan_conv2d_dgrad_pf_f32: as the plain calls; `filters` may be NULL
  *                                         (then identical to them) and is ignored by the non-Winograd paths.
  * The buffer's content is tied to the descriptor and to the OTGAN_WINO_* switches of the process.

@@ -1807,11 +1807,17 @@ static void igemm_records(EpiArgs& e, const float* a_rec, const float* a, long a
 
 static thread_local bool g_amax_written = false;
 
-static bool launch_rgbin_fwd(const otgan_conv_desc* d, int pad_t, int pad_l, const float* x, const float* wT,
-                             const float* bias, float* y, hipStream_t s) {
+// the shapes launch_rgbin_fwd takes (the caller opens its profiler scope, which counts FLOP and a launch, only then)
+static bool rgbin_fwd_takes(const otgan_conv_desc* d) {
   if (d->C != 3 || d->stride != 1 || d->upsample != 0 || d->KH != d->KW || (d->KH != 5 && d->KH != 3) ||
       d->Cout % 128 != 0 || d->W < 16 || d->W > 64)
     return false;
+  const int TR = 256 / d->W;
+  return TR >= 4 && TR <= d->H && d->H % TR == 0;
+}
+static bool launch_rgbin_fwd(const otgan_conv_desc* d, int pad_t, int pad_l, const float* x, const float* wT,
+                             const float* bias, float* y, hipStream_t s) {
+  if (!rgbin_fwd_takes(d)) return false;
   FewInArgs a;
   a.x = x; a.ldx = d->ldx; a.wT = wT; a.K = d->KH * d->KW * 3; a.bias = bias;
   a.y = y; a.ldy = d->ldy; a.coff = d->y_coff;
@@ -1849,6 +1855,13 @@ struct OuterArgs {
   long sT, sC, sJ;     // out index = t*sT + c*sC + j*sJ
 };
 
+// four channels of a row of which `left` (>= 1) exist: one 16-byte load, or the row's ragged end element by element (a wide
+// operand of 3 or 6 channels: nothing behind the last pixel's row is read)
+__device__ __forceinline__ float4 load_quad(const float* p, int left) {
+  if (left >= 4) return *reinterpret_cast<const float4*>(p);
+  return make_float4(p[0], left > 1 ? p[1] : 0.f, left > 2 ? p[2] : 0.f, 0.f);
+}
+
 // thread = 4 consecutive wide channels (one 16-byte load per pixel); the block's 8 pixel
 // streams are combined through LDS at the end.
 template <int ACT>
@@ -1884,14 +1897,14 @@ __global__ __launch_bounds__(256) void conv_outer_kernel(OuterArgs a, Taps taps)
       float4 wv;
       const float* np;
       if (a.wide_shift) {
-        wv = *reinterpret_cast<const float4*>(a.wide + spix * a.ldw + sc);
+        wv = load_quad(a.wide + spix * a.ldw + sc, a.wideC - c);
         wv.x = act_apply<ACT>(sgn * wv.x);
         wv.y = act_apply<ACT>(sgn * wv.y);
         wv.z = act_apply<ACT>(sgn * wv.z);
         wv.w = act_apply<ACT>(sgn * wv.w);
         np = a.narrow + (long)m * a.ldn;
       } else {
-        wv = *reinterpret_cast<const float4*>(a.wide + (long)m * a.ldw + c);
+        wv = load_quad(a.wide + (long)m * a.ldw + c, a.wideC - c);
         np = a.narrow + spix * a.ldn;
       }
 #pragma unroll
@@ -2320,6 +2333,10 @@ inline int pack_dhw(int dh, int dw) { return (dh << 16) | (dw & 0xffff); }
 
 // 16-byte gathers need aligned quads of effective channels to be contiguous in the source
 inline bool map_quads(const otgan_conv_desc* d) { return !doubled_act(d->preact) || d->list_quads != 0; }
+// The few-output kernels (conv_fewout_kernel and its tile / MFMA variants; conv_outer_kernel and its variants with the layer
+// input as the wide operand) decode ONE channel-map entry per aligned quad of effective channels: the quad must be four
+// consecutive source channels with one sign.  [x, -x] over C % 4 != 0 channels has a quad that straddles the two halves.
+inline bool few_quads_ok(const otgan_conv_desc* d) { return map_quads(d) && (!doubled_act(d->preact) || d->C % 4 == 0); }
 struct Geo {
   int Hin, Win, OH, OW, pad_t, pad_l, Ceff, logUp;
   bool fold;
@@ -2486,7 +2503,7 @@ WgPlan plan_wgrad(const otgan_conv_desc* d, const Geo& g) {
   p.outer = 0;
   p.chunk = p.nchunks = 0;
   if (d->upsample == 0) {
-    if (d->Cout <= 4) p.outer = 1;
+    if (d->Cout <= 4 && few_quads_ok(d)) p.outer = 1;
     else if (g.Ceff <= 4 && d->preact == OTGAN_ACT_NONE) p.outer = 2;
   }
   if (p.outer) {
@@ -2838,7 +2855,8 @@ size_t otgan_conv2d_workspace_bytes(const otgan_conv_desc* d, int which) {
   }
   if (which == 2) {
     const WgPlan p = plan_wgrad(d, g);
-    size_t slabs = (p.nsplit > 1 || p.fold) ? (size_t)p.slab_elems * p.nsplit : 0;
+    // (the few-channel kernels write their slabs to the workspace whatever their number: one chunk is one slab)
+    size_t slabs = (p.nsplit > 1 || p.fold || p.outer) ? (size_t)p.slab_elems * p.nsplit : 0;
     if (p.fold && p.nsplit > 1) slabs += (size_t)p.slab_elems;  // reduced dweff before unfolding
     const size_t gen = align_up(sizeof(float) * slabs, 256) + 256;
     return gen > s2 ? gen : s2;
@@ -3258,7 +3276,7 @@ static int conv2d_fwd_body(const otgan_conv_desc* d, const float* x, const int32
   single_class(d, g, &ct);
   for (int t = 0; t < ct.taps[0].n; ++t) ct.taps[0].boff[t] = t * g.Ceff;
   const int Ktot = ct.taps[0].n * g.Ceff;
-  if (cmap == nullptr && d->preact == OTGAN_ACT_NONE) {
+  if (cmap == nullptr && d->preact == OTGAN_ACT_NONE && rgbin_fwd_takes(d)) {
     // RGB-in layer: lanes along the output channels, weights in registers
     ProfScope ps(OTGAN_PROF_CONV_FWD, 2.0 * ga.Mtot * (double)Ktot * d->Cout, 0.0, s);
     if (launch_rgbin_fwd(d, g.pad_t, g.pad_l, x, wT, bias, y, s)) {
@@ -3267,7 +3285,7 @@ static int conv2d_fwd_body(const otgan_conv_desc* d, const float* x, const int32
     }
   }
   if (d->Cout <= 4 && d->upsample == 0 && g.Ceff % 4 == 0 && d->ldx % 4 == 0 && aligned16(x) &&
-      aligned16(wT)) {
+      aligned16(wT) && few_quads_ok(d)) {
     // RGB-out layer: vector-ALU kernel, thread = pixel (an MFMA tile would idle 29 of 32 columns)
     FewOutArgs fa;
     memset(&fa, 0, sizeof(fa));
@@ -3645,7 +3663,7 @@ int otgan_conv2d_wgrad_f32(const otgan_conv_desc* d, const float* x, const int32
   WgPlan p = plan_wgrad(d, g);
   OTGAN_CHECK_ARG(!p.vec || (aligned16(x) && aligned16(dy)), "operands must be 16-byte aligned");
   const size_t need = otgan_conv2d_workspace_bytes(d, 2);
-  if ((p.nsplit > 1 || p.fold) && (!workspace || workspace_bytes < need)) {
+  if ((p.nsplit > 1 || p.fold || p.outer) && (!workspace || workspace_bytes < need)) {
     otgan_set_error("conv2d wgrad workspace too small: need %zu, got %zu", need, workspace_bytes);
     return OTGAN_ERR_WORKSPACE;
   }
