@@ -621,4 +621,49 @@ int otgan_batch_from_u8_f32(const uint8_t* store, long n_images, int SH, int SW,
 int otgan_augment_fwd_f32(const float* x, long rows, int S, const float* u, int policy, float* y, void* stream);
 int otgan_augment_bwd_f32(const float* dy, long rows, int S, const float* u, int policy, float* dx, void* stream);
 
+/*
+ * The sliced Wasserstein distance on Laplacian-pyramid patches (Karras et al. 2018, "Progressive Growing of GANs", section 5;
+ * csrc/swd.hip, utils/swd.py): the device stages between two sets of uint8 images and the per-direction sorts.  The descriptor
+ * matrix (n P x 147 floats per level and set) is never written.
+ *   img: NHWC uint8 [n][S][S][3], contiguous, 4-byte aligned.  S in {16, 32, 64}; any other S returns OTGAN_ERR_UNSUPPORTED.
+ *   Levels: L = log2(S / 16) + 1 = otgan_swd_levels(S) (0 for an unsupported S); level l has side S_l = S >> l, the last is 16 x 16.
+ * Pyramid of one image, per channel, in fp32:
+ *   g = [1 4 6 4 1] (x) [1 4 6 4 1] / 256;  border = mirror WITHOUT repeating the edge pixel (index -1 -> 1, s -> s - 2:
+ *   scipy.ndimage's mode='mirror');  down(x) = (g * x)[::2, ::2];  up(x) = (4 g) * z with z = x on the even pixels of a zero
+ *   image of twice the side.
+ *   pyr[0] = float(img);  for i = 1 ... L - 1:  pyr[i] = down(pyr[i - 1]),  then  pyr[i - 1] -= up(pyr[i]).  The last level stays
+ *   Gaussian.  A 5 x 5 sum is taken with the integer weights in the order dy outer, dx inner and scaled once; with uint8 inputs
+ *   every stage but up() of the 16 x 16 level at S = 64 is exact in fp32.
+ * otgan_swd_pyramid_u8: out fp32 [n][S_l][S_l][3] (16-byte aligned) = level `level` of every image.  A staged entry for tests.
+ * Descriptors: pos int32 [L][n][P][2] (device) holds the top-left (y, x) of P patches of 7 x 7 x 3 per image and level,
+ *   0 <= y, x <= S_l - 7 (the caller's to guarantee; a value outside is moved to the nearest bound, so nothing is read out of
+ *   bounds).  A descriptor is the patch flattened in [channel][dy][dx] order: 147 values, element e = (c 7 + dy) 7 + dx.
+ * otgan_swd_channel_stats_u8: for every level l and channel c, over ALL n P 49 descriptor elements of that channel,
+ *   mean[l][c] = sum x / N,   inv_std[l][c] = 1 / sqrt(sum x^2 / N - mean^2)   (population std, ddof = 0; fp64, stored as fp32
+ *   [L][3]).  A zero variance gives +inf -- and NaN projections, loud.  The statistics are those of the EXACT pyramid (built in
+ *   fp64 here; the fp32 pyramid's one inexact stage would show in the near-zero mean of a Laplacian level).  Per image the sums
+ *   are taken in fp64 in a fixed order;
+ *   across images they are added EXACTLY (every level value is a multiple of 2^-22, so the per-image sums scale to integers that
+ *   are added in int64): the outputs do not depend on the order of the images.  n >= 1, n P <= 2^27.  Two launches on `stream`,
+ *   no atomics, no host synchronisation.  workspace: otgan_swd_workspace_bytes(n, S, P) bytes, 8-byte aligned (the per-image
+ *   sums); OTGAN_ERR_WORKSPACE when smaller.
+ * otgan_swd_project_u8: for level `level`, every direction j < nd, image i < n and patch p < P
+ *   proj[j][i P + p] = sum over e of ((x_e - mean[level][c_e]) inv_std[level][c_e]) dirs[j][e]
+ *   with dirs fp32 [nd][147] and proj fp32 [nd][ldp], ldp >= n P; columns >= n P are not touched.  fp32, one fma per element in
+ *   the order e = 0 ... 146: the bits of an output depend on the image, its positions, mean, inv_std and dirs[j] alone -- not on
+ *   n, nd, or which images and directions share a call (a caller that splits the images passes each part's own pos [L][n'][P][2]
+ *   and proj + i0 P).  One launch; nd == 0 or n == 0 returns OTGAN_OK without one.
+ * otgan_swd_row_l1_f64: out[r] = (sum over k < m of |a[r][k] - b[r][k]|) / m for r < rows, a and b fp32 with row strides
+ *   lda, ldb >= m, converted to fp64 before the subtraction; a fixed summation order per row that depends on m only.
+ * An argument error returns nonzero with a message before any launch.
+ */
+int otgan_swd_levels(int S);
+int otgan_swd_pyramid_u8(const uint8_t* img, long n, int S, int level, float* out, void* stream);
+size_t otgan_swd_workspace_bytes(long n, int S, int P);
+int otgan_swd_channel_stats_u8(const uint8_t* img, long n, int S, const int32_t* pos, int P, float* mean, float* inv_std,
+                               void* workspace, size_t workspace_bytes, void* stream);
+int otgan_swd_project_u8(const uint8_t* img, long n, int S, const int32_t* pos, int P, int level, const float* mean,
+                         const float* inv_std, const float* dirs, int nd, float* proj, long ldp, void* stream);
+int otgan_swd_row_l1_f64(const float* a, long lda, const float* b, long ldb, int rows, long m, double* out, void* stream);
+
 #endif /* OTGAN_LAYERS_H */

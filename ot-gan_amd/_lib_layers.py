@@ -135,4 +135,10 @@ SIGNATURES = {
                                         c_fp, c_long, c_fp]),
     "otgan_augment_fwd_f32": (c_int, [c_fp, c_long, c_int, c_fp, c_int, c_fp, c_fp]),
     "otgan_augment_bwd_f32": (c_int, [c_fp, c_long, c_int, c_fp, c_int, c_fp, c_fp]),
+    "otgan_swd_levels": (c_int, [c_int]),
+    "otgan_swd_pyramid_u8": (c_int, [c_fp, c_long, c_int, c_int, c_fp, c_fp]),
+    "otgan_swd_workspace_bytes": (c_size_t, [c_long, c_int, c_int]),
+    "otgan_swd_channel_stats_u8": (c_int, [c_fp, c_long, c_int, c_fp, c_int, c_fp, c_fp, c_fp, c_size_t, c_fp]),
+    "otgan_swd_project_u8": (c_int, [c_fp, c_long, c_int, c_fp, c_int, c_int, c_fp, c_fp, c_fp, c_int, c_fp, c_long, c_fp]),
+    "otgan_swd_row_l1_f64": (c_int, [c_fp, c_long, c_fp, c_long, c_int, c_long, c_fp, c_fp]),
 }

@@ -1919,3 +1919,107 @@ def augment(x, u, policy):
 def augment_transpose(dy, u, policy):
     """T^T dy: the backward launch of `augment` on its own (no autograd)."""
     return _augment_launch(_lib.lib().otgan_augment_bwd_f32, "augment_bwd", dy, u, policy)
+
+
+SWD_DESC = 147             # 7 x 7 x 3 values of a patch descriptor (include/otgan_layers.h)
+
+
+def swd_levels(S):
+    """Pyramid levels of S x S images, log2(S / 16) + 1; a ValueError for any S but 16, 32 and 64."""
+    L = _lib.lib().otgan_swd_levels(int(S))
+    if L == 0:
+        raise ValueError("the sliced Wasserstein pyramid is defined for images of 16, 32 and 64 pixels a side, not %d" % S)
+    return L
+
+
+def _swd_images(img, name):
+    if not (torch.is_tensor(img) and img.is_cuda):
+        raise _lib.OtganError("%s takes CUDA (MI355X) tensors; there is no CPU fallback" % name)
+    if not (img.dtype == torch.uint8 and img.dim() == 4 and img.shape[1] == img.shape[2] and img.shape[3] == 3):
+        raise ValueError("%s takes uint8 [n, S, S, 3] images, found %s %s" % (name, img.dtype, tuple(img.shape)))
+    L = swd_levels(img.shape[1])
+    return img.contiguous(), img.shape[0], img.shape[1], L
+
+
+def _swd_positions(pos, L, n, name, device):
+    if not (torch.is_tensor(pos) and pos.is_cuda and pos.device == device):
+        raise _lib.OtganError("%s takes its positions as a CUDA (MI355X) tensor on %s; there is no CPU fallback" % (name, device))
+    if not (pos.dtype == torch.int32 and pos.dim() == 4 and tuple(pos.shape[:2]) == (L, n) and pos.shape[2] >= 1
+            and pos.shape[3] == 2):
+        raise ValueError("%s: positions must be int32 [%d, %d, P, 2], found %s %s" % (name, L, n, pos.dtype, tuple(pos.shape)))
+    return pos.contiguous(), pos.shape[2]
+
+
+def swd_pyramid(img, level):
+    """Level `level` of the Laplacian pyramid of uint8 images [n, S, S, 3] -> fp32 [n, S_l, S_l, 3] (otgan_swd_pyramid_u8)."""
+    img, n, S, L = _swd_images(img, "swd_pyramid")
+    if not 0 <= level < L:
+        raise ValueError("swd_pyramid: level %d of %d" % (level, L))
+    out = torch.empty(n, S >> level, S >> level, 3, dtype=torch.float32, device=img.device)
+    with torch.cuda.device(img.device):
+        _lib.check(_lib.lib().otgan_swd_pyramid_u8(img.data_ptr(), n, S, int(level), out.data_ptr(), _lib.stream_ptr()), "swd_pyramid")
+    return out
+
+
+def swd_channel_stats(img, pos):
+    """(mean, inv_std), fp32 [L, 3] each: the per-level, per-channel statistics of the patch descriptors of uint8 images
+    [n, S, S, 3] at positions int32 [L, n, P, 2] (otgan_swd_channel_stats_u8).  No host synchronisation."""
+    img, n, S, L = _swd_images(img, "swd_channel_stats")
+    if n == 0:
+        raise ValueError("swd_channel_stats: statistics of no image")
+    pos, P = _swd_positions(pos, L, n, "swd_channel_stats", img.device)
+    mean = torch.empty(L, 3, dtype=torch.float32, device=img.device)
+    inv_std = torch.empty(L, 3, dtype=torch.float32, device=img.device)
+    with torch.cuda.device(img.device):
+        nbytes = _lib.lib().otgan_swd_workspace_bytes(n, S, P)
+        ws = workspace(nbytes, img.device)
+        _lib.check(_lib.lib().otgan_swd_channel_stats_u8(img.data_ptr(), n, S, pos.data_ptr(), P, mean.data_ptr(), inv_std.data_ptr(),
+                                                         ws.data_ptr(), ws.numel(), _lib.stream_ptr()), "swd_channel_stats")
+    return mean, inv_std
+
+
+def swd_project(img, pos, level, mean, inv_std, dirs, out=None, col0=0):
+    """Projections of the normalised patch descriptors of level `level` on `dirs` fp32 [nd, 147] (otgan_swd_project_u8):
+    out[j, col0 + i P + p], out fp32 [nd, ld] with ld >= col0 + n P (allocated [nd, n P] when None).  Columns outside
+    [col0, col0 + n P) are not touched."""
+    img, n, S, L = _swd_images(img, "swd_project")
+    pos, P = _swd_positions(pos, L, n, "swd_project", img.device)
+    if not 0 <= level < L:
+        raise ValueError("swd_project: level %d of %d" % (level, L))
+    _need_cuda(mean, inv_std, dirs, out)
+    for t, name in ((mean, "mean"), (inv_std, "inv_std")):
+        if not (t.dtype == torch.float32 and tuple(t.shape) == (L, 3) and t.is_contiguous() and t.device == img.device):
+            raise ValueError("swd_project: %s must be contiguous float32 [%d, 3] on %s, found %s %s" % (name, L, img.device, t.dtype, tuple(t.shape)))
+    if not (dirs.dtype == torch.float32 and dirs.dim() == 2 and dirs.shape[1] == SWD_DESC and dirs.is_contiguous()
+            and dirs.device == img.device):
+        raise ValueError("swd_project: dirs must be contiguous float32 [nd, %d] on %s, found %s %s" % (SWD_DESC, img.device, dirs.dtype, tuple(dirs.shape)))
+    nd = dirs.shape[0]
+    if out is None:
+        out = torch.empty(nd, col0 + n * P, dtype=torch.float32, device=img.device)
+    if not (out.dtype == torch.float32 and out.dim() == 2 and out.shape[0] == nd and out.shape[1] >= col0 + n * P and col0 >= 0
+            and out.device == img.device and (out.stride(1) == 1 or out.shape[1] == 1) and (nd <= 1 or out.stride(0) >= out.shape[1])):
+        raise ValueError("swd_project: out must be float32 [%d, >= %d] on %s with unit column stride, found %s %s"
+                         % (nd, col0 + n * P, img.device, out.dtype, tuple(out.shape)))
+    ldp = out.stride(0) if nd > 1 else out.shape[1]
+    with torch.cuda.device(img.device):
+        _lib.check(_lib.lib().otgan_swd_project_u8(img.data_ptr(), n, S, pos.data_ptr(), P, int(level), mean.data_ptr(),
+                                                   inv_std.data_ptr(), dirs.data_ptr(), nd, out.data_ptr() + 4 * int(col0),
+                                                   ldp, _lib.stream_ptr()), "swd_project")
+    return out
+
+
+def swd_row_l1(a, b):
+    """fp64 [rows]: mean over the columns of |a - b| for fp32 [rows, m] a, b with unit column stride (otgan_swd_row_l1_f64)."""
+    _need_cuda(a, b)
+    if not (torch.is_tensor(a) and torch.is_tensor(b) and a.dtype == torch.float32 and b.dtype == torch.float32 and a.dim() == 2
+            and a.shape == b.shape and a.shape[1] >= 1 and a.device == b.device):
+        raise ValueError("swd_row_l1 takes two float32 [rows, m] tensors of one shape and device")
+    if a.stride(1) != 1 or a.stride(0) < a.shape[1]:
+        a = a.contiguous()
+    if b.stride(1) != 1 or b.stride(0) < b.shape[1]:
+        b = b.contiguous()
+    out = torch.empty(a.shape[0], dtype=torch.float64, device=a.device)
+    with torch.cuda.device(a.device):
+        _lib.check(_lib.lib().otgan_swd_row_l1_f64(a.data_ptr(), a.stride(0), b.data_ptr(), b.stride(0), a.shape[0], a.shape[1],
+                                                   out.data_ptr(), _lib.stream_ptr()), "swd_row_l1")
+    return out

@@ -26,7 +26,10 @@ same bits as the default host path, step for step (same host and device random s
 --augment color,translation,cutout (utils/augment.py, ops.augment: differentiable augmentation, Zhao et al. 2020 -- one random
 colour / translation / cutout transform per image in front of every critic pass of a training step, real and generated, with
 the generator's gradient taken through it; the lever against a critic that memorises a small training set.  Samples, metrics,
-the probe and the initialisation pass are never augmented; '' = off, and the step is then the reference's bit for bit).
+the probe and the initialisation pass are never augmented; '' = off, and the step is then the reference's bit for bit),
+--swd_samples / --swd_patches / --swd_dirs / --swd_repeats (utils/swd.py: the sliced Wasserstein distance x 1e3 per
+Laplacian-pyramid level between generated and training images, Karras et al. 2018 -- the one sample metric that needs no
+--inception_model; at the --eval_every cadence, for the live and the EMA generator, without moving the training run).
 
 Checkpoints (`<save_dir>/med_gan_params-<epoch>`, the reference's naming, train.py:275-277) are torch pickles
 of {variable name: tensor} plus optimiser moments / step count and EMA shadows (which the reference's
@@ -133,6 +136,14 @@ def build_parser():
                         "2020): a comma-separated subset of color,translation,cutout in any order, e.g. "
                         "'color,translation,cutout'; the generator's gradient flows through the transform.  For small training "
                         "sets.  '' = off (the reference's step)")
+    p.add_argument('--swd_samples', type=int, default=0,
+                   help='report the sliced Wasserstein distance x 1e3 per Laplacian-pyramid level (Karras et al. 2018; '
+                        'utils/swd.py) between this many generated and as many training images at the --eval_every cadence, for '
+                        'the live and the EMA generator.  Needs no --inception_model.  The paper uses 16384; cut, with a notice, '
+                        'to the number of training images.  0 = off')
+    p.add_argument('--swd_patches', type=int, default=128, help='7 x 7 patches per image and pyramid level (the paper: 128)')
+    p.add_argument('--swd_dirs', type=int, default=128, help='random directions per repeat (the paper: 128)')
+    p.add_argument('--swd_repeats', type=int, default=4, help='repeats, each with fresh directions (the paper: 4)')
     return p
 
 
@@ -375,6 +386,50 @@ def probe_hook(model, args, state, rank=0, world=1):
     return acc, right_1 / n
 
 
+def swd_state(args, trainx, dev, rank=0, world=1):
+    """--swd_samples: what the sliced Wasserstein hook keeps for the run -- {"real": utils.swd.SwdReal, the sorted projections
+    of the first n training images on this rank's contiguous share of the --swd_repeats x --swd_dirs directions, "n",
+    "swd_min" / "swd_iter"}.  Positions (separate draws for the real and the generated side) and directions come ONCE per run
+    from a private host generator seeded with --seed, the same on every rank, so evaluations are comparable across epochs; no
+    draw touches the run's own random streams.  An image size without a pyramid is a ValueError here, before the first step."""
+    from .utils import features, swd
+    swd.levels(args.image_size)
+    n = min(args.swd_samples, trainx.shape[0])
+    if rank == 0 and n < args.swd_samples:
+        print('--swd_samples %d: cut to the %d training images' % (args.swd_samples, n))
+    if hasattr(trainx, "rows"):      # the stored uint8 where the store is what the model sees, the quantised rows otherwise
+        real = trainx.store[:n] if trainx.factor == 1 else torch.cat(
+            [swd.quantise(trainx.rows(i, min(i + 1000, n))) for i in range(0, n, 1000)])
+    else:
+        real = torch.from_numpy(swd.quantise(trainx[:n])).to(dev)
+    g = torch.Generator().manual_seed(args.seed)
+    pos_real = swd.positions(n, args.image_size, args.swd_patches, g)
+    pos_gen = swd.positions(n, args.image_size, args.swd_patches, g)
+    dirs = swd.directions(args.swd_repeats, args.swd_dirs, g)
+    made = swd.SwdReal(real, pos_real, dirs, pos_gen=pos_gen, dir_range=features.share(dirs.shape[0], rank, world))
+    if rank == 0:
+        print('sliced Wasserstein distance: %d generated against %d training images, %d patches per image and level, %d '
+              'directions, %d levels; sorted projections of the real side kept on the device (%.1f MB per rank)'
+              % (n, n, args.swd_patches, dirs.shape[0], made.L, made.nbytes / 1e6))
+    return {"real": made, "n": n}
+
+
+def swd_hook(model, args, state, rank=0, world=1):
+    """The sliced Wasserstein distance of the live and the EMA generator against the training images (utils/swd.py), whether or
+    not there is an --inception_model.  Every rank takes part: it samples its share of the images (swd.sample_images: fixed
+    latents, the device generator's state saved and restored, so the training run does not move), the uint8 images are
+    gathered, each rank computes its share of the directions and the table is gathered; all ranks get the same numbers, rank 0
+    prints them."""
+    from .utils import swd
+    metric = swd.SwdMetric(state["real"], args, state, rank, world)
+    out = {}
+    for tag, ema in (("", False), ("EMA ", True)):
+        images = swd.sample_images(model, state["n"], args.seed, ema=ema, rank=rank, world=world)
+        out[tag.strip() or "live"] = metric.evaluate(images, tag)
+    metric.close()
+    return out
+
+
 def load_cifar(data_dir, subset='train'):
     """Pickled CIFAR-10 python batches under <data_dir>/cifar-10-python/cifar-10-batches-py
     (the layout the reference's data/cifar10_data.py:40-53 reads; no download here)."""
@@ -505,6 +560,7 @@ def main(argv=None, self_launch=False):
     if args.pr_neighbours > 0:
         score_state.update(real_pr_state(args, classifier, trainx, rank, world, score_state.get("kid_real")))
     probe_st = probe_state(args, trainx, dev, rank, world) if args.probe_every > 0 else None
+    swd_st = swd_state(args, trainx, dev, rank, world) if args.swd_samples > 0 else None
     start_time = time.time()
     total = 0
     for epoch in range(current_epoch, 1000000):
@@ -543,6 +599,9 @@ def main(argv=None, self_launch=False):
         if probe_st is not None and (epoch + 1) % args.probe_every == 0 and epoch != current_epoch:
             probe_st["epoch"] = epoch
             probe_hook(model, args, probe_st, rank, world)
+        if swd_st is not None and (epoch + 1) % args.eval_every == 0 and epoch != current_epoch:
+            swd_st["epoch"] = epoch
+            swd_hook(model, args, swd_st, rank, world)
         if rank == 0:
             print("Iteration %d, time = %ds, train distance before gen = %.6f, train distance before disc = %.6f, "
                   "avg matching entropy = %.6f" % (epoch, time.time() - begin, mean_dist_gen[-1],
