@@ -562,6 +562,37 @@ int otgan_topk_dot_f64(int nq, int ny, int C, const float* q, int ldq, const flo
                        int32_t* index, double* score, void* workspace, size_t workspace_bytes, void* stream);
 
 /*
+ * Exact nearest neighbours of uint8 rows (images in pixel space) BY IDENTITY, for the authenticity score
+ * (utils/authenticity.py), on the int8 matrix pipe (csrc/pixnn.hip); the distance matrix is never written.  With
+ * d(a, b) = sum_d (a_d - b_d)^2 over the raw uint8 values, for every query row i < nq over the columns j < ny with
+ * j != self0 + i (self0 = -1: no column is excluded):
+ *   index[i][0 .. k) = the columns of the k smallest d(q_i, y_j),
+ *   dist[i][0 .. k)  = those values,
+ * sorted by distance ascending, equal distances by the SMALLER COLUMN first: a total order, and every distance is an exact
+ * integer, so the outputs are a function of the inputs alone, bit for bit -- not of the order in which columns are
+ * visited, of a row's place in the call or of how the columns are split over workgroups; no atomics, no tolerance.  Slots
+ * beyond the number of counted columns hold index -1 and dist -1.  The exclusion is by POSITION: another row with the
+ * same values is returned, with distance 0 (also when self0 + i >= ny: nothing is excluded then).
+ * q, y: uint8 rows of D values with row strides ldq, ldy >= D in bytes, multiples of 16, row pointers 16-byte aligned;
+ * D % 16 == 0, 16 <= D <= 49152 (128 x 128 x 3); 1 <= k <= 8; 0 <= ny <= 2^31 - 2; index: int32 [nq][k], dist: int64
+ * [nq][k], both OVERWRITTEN.
+ * Arithmetic and its bounds: each byte x enters the product as the int8 x - 128 (x ^ 0x80), a common shift that changes no
+ * difference, and d = |a|^2 + |b|^2 - 2 a.b with a.b from v_mfma_i32_16x16x64_i8 and the norms from a pre-pass.
+ *   |a.b| and the norms are at most D 2^14 <= 49152 x 16384 = 805 306 368 < 2^31: every int32 partial sum is exact;
+ *   d is at most D 255^2 = 3 196 108 800 at D = 49152: it does NOT fit int32 and does fit uint32.  The three terms are added
+ *   in unsigned 32 bits (the true value is in range, so the wrapped sum is the value) and ordered as the 64-bit key
+ *   (d << 32) | j, whose plain unsigned order is the pair order above; the key 2^64 - 1 marks an empty slot, above every
+ *   real key.  dist leaves as int64.
+ * workspace: otgan_nn_u8_workspace_bytes(nq, ny, k) bytes, 8-byte aligned -- 8 splits nq k bytes of keys (k per column
+ * split and query row), then 4 (nq + ny) bytes of norms rounded up to 8; OTGAN_ERR_WORKSPACE when smaller.  nq == 0
+ * returns OTGAN_OK; ny == 0 fills every slot with (-1, -1) (no workspace needed).  An argument error returns
+ * OTGAN_ERR_INVALID without touching the outputs.
+ */
+size_t otgan_nn_u8_workspace_bytes(int nq, int ny, int k);
+int otgan_nn_u8(int nq, int ny, int D, const uint8_t* q, long ldq, const uint8_t* y, long ldy, int k, int self0,
+                int32_t* index, int64_t* dist, void* workspace, size_t workspace_bytes, void* stream);
+
+/*
  * The training batch from a device-resident uint8 dataset in ONE launch (csrc/data.hip; utils/data.py): gather by the
  * epoch's permutation, per-image horizontal flip, uint8 -> [-1, 1] and an optional integer box-downsample -- what the
  * reference does on the host per step (train.py:158,163-170,209-211).

@@ -131,6 +131,8 @@ SIGNATURES = {
     "otgan_knn_f64": (c_int, [c_int, c_int, c_int, c_fp, c_int, c_fp, c_int, c_int, c_int, c_fp, c_fp, c_fp, c_fp, c_size_t, c_fp]),
     "otgan_topk_dot_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
     "otgan_topk_dot_f64": (c_int, [c_int, c_int, c_int, c_fp, c_int, c_fp, c_int, c_int, c_int, c_fp, c_fp, c_fp, c_size_t, c_fp]),
+    "otgan_nn_u8_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "otgan_nn_u8": (c_int, [c_int, c_int, c_int, c_fp, c_long, c_fp, c_long, c_int, c_int, c_fp, c_fp, c_fp, c_size_t, c_fp]),
     "otgan_batch_from_u8_f32": (c_int, [c_fp, c_long, c_int, c_int, c_fp, c_long, c_fp, c_int, c_int, c_fp, c_fp, c_int,
                                         c_fp, c_long, c_fp]),
     "otgan_augment_fwd_f32": (c_int, [c_fp, c_long, c_int, c_fp, c_int, c_fp, c_fp]),

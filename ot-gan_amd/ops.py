@@ -2023,3 +2023,51 @@ def swd_row_l1(a, b):
         _lib.check(_lib.lib().otgan_swd_row_l1_f64(a.data_ptr(), a.stride(0), b.data_ptr(), b.stride(0), a.shape[0], a.shape[1],
                                                    out.data_ptr(), _lib.stream_ptr()), "swd_row_l1")
     return out
+
+
+NN_U8_MAX_K, NN_U8_MAX_D = 8, 49152
+
+
+def _nn_u8_rows(x, name):
+    """x as otgan_nn_u8 reads it: uint8 CUDA [n, D] (or [n, S, S, 3], flattened) in 16-byte pieces of a row; a column slice
+    of a wider buffer passes its row stride on, anything that cannot be read that way is copied."""
+    if not (torch.is_tensor(x) and x.is_cuda):
+        raise _lib.OtganError("nn_u8 takes CUDA (MI355X) uint8 tensors; there is no CPU fallback")
+    if x.dtype != torch.uint8 or x.dim() not in (2, 4) or (x.dim() == 4 and (x.shape[1] != x.shape[2] or x.shape[3] != 3)):
+        raise ValueError("nn_u8: %s must be uint8 [n, D] or [n, S, S, 3], found %s %s" % (name, x.dtype, tuple(x.shape)))
+    if x.dim() == 4:
+        x = x.contiguous().view(x.shape[0], -1)
+    D = x.shape[1]
+    if D % 16 or not 16 <= D <= NN_U8_MAX_D:
+        raise ValueError("nn_u8: %s has rows of %d values; a multiple of 16 in 16 ... %d" % (name, D, NN_U8_MAX_D))
+    if x.stride(1) != 1 or x.stride(0) < D or x.stride(0) % 16 or x.data_ptr() % 16:
+        x = x.contiguous()
+    return x
+
+
+def nn_u8(q, y, k, self0=-1):
+    """(index int32 [nq, k], dist int64 [nq, k]): per row of q the rows of y with the k smallest squared Euclidean distances
+    over the raw uint8 values, by distance ascending, equal distances by the smaller row first; (-1, -1) where fewer were
+    counted.  Row self0 + i of y is skipped for row i of q (self0 = -1: none).  Exact integers from the int8 matrix pipe
+    (otgan_nn_u8); q, y: uint8 CUDA [n, D] or [n, S, S, 3]."""
+    q, y = _nn_u8_rows(q, "q"), _nn_u8_rows(y, "y")
+    if q.shape[1] != y.shape[1] or q.device != y.device:
+        raise ValueError("nn_u8: q %s and y %s must have the same row length and device" % (tuple(q.shape), tuple(y.shape)))
+    k, self0 = int(k), int(self0)
+    if not 1 <= k <= NN_U8_MAX_K:
+        raise ValueError("nn_u8: %d neighbours: between 1 and %d" % (k, NN_U8_MAX_K))
+    if self0 < -1:
+        raise ValueError("nn_u8: self0 %d >= -1" % self0)
+    nq, ny, D = q.shape[0], y.shape[0], q.shape[1]
+    index = torch.empty(nq, k, dtype=torch.int32, device=q.device)
+    dist = torch.empty(nq, k, dtype=torch.int64, device=q.device)
+    if nq == 0:
+        return index, dist
+    L = _lib.lib()
+    with torch.cuda.device(q.device):
+        nbytes = L.otgan_nn_u8_workspace_bytes(nq, ny, k)
+        ws = workspace(nbytes, q.device)
+        _lib.check(L.otgan_nn_u8(nq, ny, D, q.data_ptr(), q.stride(0) if nq > 1 else D, y.data_ptr() if ny else None,
+                                 y.stride(0) if ny > 1 else D, k, self0, index.data_ptr(), dist.data_ptr(), ws.data_ptr(),
+                                 ws.numel(), _lib.stream_ptr()), "nn_u8")
+    return index, dist

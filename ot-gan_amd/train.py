@@ -29,7 +29,11 @@ the generator's gradient taken through it; the lever against a critic that memor
 the probe and the initialisation pass are never augmented; '' = off, and the step is then the reference's bit for bit),
 --swd_samples / --swd_patches / --swd_dirs / --swd_repeats (utils/swd.py: the sliced Wasserstein distance x 1e3 per
 Laplacian-pyramid level between generated and training images, Karras et al. 2018 -- the one sample metric that needs no
---inception_model; at the --eval_every cadence, for the live and the EMA generator, without moving the training run).
+--inception_model; at the --eval_every cadence, for the live and the EMA generator, without moving the training run),
+--authenticity_samples / --authenticity_neighbours / --authenticity_train_samples (utils/authenticity.py: is the generator
+copying the training set?  Exact pixel-space nearest training images of generated samples on the int8 matrix pipe, the
+authenticity score of Alaa et al. 2022 beside a held-out baseline, and nn_sample<epoch>.png: the samples nearest to the
+training set, each beside its nearest training images; same cadence, same fixed samples as --swd_samples).
 
 Checkpoints (`<save_dir>/med_gan_params-<epoch>`, the reference's naming, train.py:275-277) are torch pickles
 of {variable name: tensor} plus optimiser moments / step count and EMA shadows (which the reference's
@@ -144,6 +148,15 @@ def build_parser():
     p.add_argument('--swd_patches', type=int, default=128, help='7 x 7 patches per image and pyramid level (the paper: 128)')
     p.add_argument('--swd_dirs', type=int, default=128, help='random directions per repeat (the paper: 128)')
     p.add_argument('--swd_repeats', type=int, default=4, help='repeats, each with fresh directions (the paper: 4)')
+    p.add_argument('--authenticity_samples', type=int, default=0,
+                   help='report the authenticity score (Alaa et al. 2022; utils/authenticity.py) of this many generated images '
+                        'from their exact nearest training images in pixel space, at the --eval_every cadence, for the live and '
+                        'the EMA generator, and write nn_sample<epoch>.png: the samples nearest to the training set beside their '
+                        'nearest training images.  Needs no --inception_model.  0 = off')
+    p.add_argument('--authenticity_neighbours', type=int, default=3,
+                   help='nearest training images shown per sample on the sheet (1 ... 8); the score uses the first')
+    p.add_argument('--authenticity_train_samples', type=int, default=50000,
+                   help='training images that are searched: the first N')
     return p
 
 
@@ -430,6 +443,65 @@ def swd_hook(model, args, state, rank=0, world=1):
     return out
 
 
+def _u8_at_model_size(trainx, n, dev):
+    """The first n training images as the model sees them, uint8 on the device: the stored uint8 where the store is what the
+    model sees, the quantised rows otherwise (as swd_state)."""
+    from .utils import swd
+    if hasattr(trainx, "rows"):
+        return trainx.store[:n] if trainx.factor == 1 else torch.cat(
+            [swd.quantise(trainx.rows(i, min(i + 1000, n))) for i in range(0, n, 1000)])
+    return torch.from_numpy(swd.quantise(trainx[:n])).to(dev)
+
+
+def authenticity_state(args, trainx, dev, rank=0, world=1):
+    """--authenticity_samples: what the authenticity hook keeps for the run -- {"bank": the first
+    --authenticity_train_samples training images as uint8 on the device, "radii": each one's squared distance to its nearest
+    other bank image (computed once, every rank its share), "held": the score of the first held-out images (cifar10 /
+    imagenet64; None for npy and --synthetic, said once), "n"}.  A bank of fewer than 2 images is a ValueError here, before
+    the first step."""
+    from .utils import authenticity, data as udata
+    n_bank = min(args.authenticity_train_samples, trainx.shape[0])
+    if n_bank < 2:
+        raise ValueError("--authenticity_samples needs a bank of at least 2 training images: it has %d" % n_bank)
+    bank = _u8_at_model_size(trainx, n_bank, dev)
+    radii = authenticity.radii(bank, rank, world)
+    state = {"bank": bank, "radii": radii, "n": args.authenticity_samples, "held": None}
+    if rank == 0:
+        print('authenticity: %d generated against %d training images, %d of which have an exact duplicate among them'
+              % (args.authenticity_samples, n_bank, int((radii == 0).sum())))
+    if args.synthetic or args.dataset == 'npy':
+        if rank == 0:
+            print('--authenticity_samples: %s has no held-out subset; the authenticity score is printed without a held-out '
+                  'baseline' % ('--synthetic data' if args.synthetic else args.data_dir))
+        return state
+    held = udata.load_u8(args.dataset, args.data_dir, 'test')[:args.authenticity_samples]
+    held = _u8_at_model_size(udata.DeviceDataset(np.ascontiguousarray(held), dev, args.image_size), held.shape[0], dev)
+    metric = authenticity.AuthenticityMetric(bank, radii, {}, rank, world)
+    state["held"] = m = metric.measure(held)
+    if rank == 0:
+        print('held-out authenticity was %.4f, median nearest distance was %.2f, exact copies %d, %d held-out against %d '
+              'training images' % (m["authentic"] / m["n"], authenticity.rms(m["median"], metric.D), m["copies"], m["n"], n_bank))
+    return state
+
+
+def authenticity_hook(model, args, state, rank=0, world=1):
+    """The authenticity of the live and the EMA generator against the training images (utils/authenticity.py), whether or not
+    there is an --inception_model.  The samples are swd.sample_images' (fixed latents, the device generator's state saved and
+    restored: the training run does not move); each rank searches its share of them, all ranks get the same numbers, rank 0
+    prints them and writes the nearest-neighbour sheets."""
+    from .utils import authenticity, swd
+    metric = authenticity.AuthenticityMetric(state["bank"], state["radii"], state, rank, world, held=state["held"])
+    out = {}
+    for tag, ema in (("", False), ("EMA ", True)):
+        images = swd.sample_images(model, state["n"], args.seed, ema=ema, rank=rank, world=world)
+        out[tag.strip() or "live"] = m = metric.evaluate(images, tag, k=args.authenticity_neighbours)
+        if rank == 0:
+            authenticity.save_png(authenticity.sheet(images, state["bank"], m["index"], m["dist"]),
+                                  os.path.join(args.save_dir, '%snn_sample%d.png' % ('ema_' if ema else '', state["epoch"])))
+    metric.close()
+    return out
+
+
 def load_cifar(data_dir, subset='train'):
     """Pickled CIFAR-10 python batches under <data_dir>/cifar-10-python/cifar-10-batches-py
     (the layout the reference's data/cifar10_data.py:40-53 reads; no download here)."""
@@ -491,6 +563,12 @@ def main(argv=None, self_launch=False):
         policy = augment.parse_policy(args.augment)
     except ValueError as e:
         raise ValueError("--augment: %s" % e) from None
+    if args.authenticity_samples > 0:
+        from .utils import authenticity
+        try:
+            authenticity.check_neighbours(args.authenticity_neighbours)
+        except ValueError as e:
+            raise ValueError("--authenticity_neighbours: %s" % e) from None
     from . import parallel
     from .trainer import OTGAN
     if not parallel.launched() and (self_launch or args.ranks):
@@ -561,6 +639,7 @@ def main(argv=None, self_launch=False):
         score_state.update(real_pr_state(args, classifier, trainx, rank, world, score_state.get("kid_real")))
     probe_st = probe_state(args, trainx, dev, rank, world) if args.probe_every > 0 else None
     swd_st = swd_state(args, trainx, dev, rank, world) if args.swd_samples > 0 else None
+    auth_st = authenticity_state(args, trainx, dev, rank, world) if args.authenticity_samples > 0 else None
     start_time = time.time()
     total = 0
     for epoch in range(current_epoch, 1000000):
@@ -602,6 +681,9 @@ def main(argv=None, self_launch=False):
         if swd_st is not None and (epoch + 1) % args.eval_every == 0 and epoch != current_epoch:
             swd_st["epoch"] = epoch
             swd_hook(model, args, swd_st, rank, world)
+        if auth_st is not None and (epoch + 1) % args.eval_every == 0 and epoch != current_epoch:
+            auth_st["epoch"] = epoch
+            authenticity_hook(model, args, auth_st, rank, world)
         if rank == 0:
             print("Iteration %d, time = %ds, train distance before gen = %.6f, train distance before disc = %.6f, "
                   "avg matching entropy = %.6f" % (epoch, time.time() - begin, mean_dist_gen[-1],

@@ -836,7 +836,8 @@ def default_args(**over):
              inception_model='', ranks=0, step_graph=None, fid_stats='', fid_real_samples=0, dataset='cifar10',
              data_on_device=False, kid_subsets=0, kid_subset_size=1000, kid_real_samples=0,
              pr_neighbours=0, pr_real_samples=0, probe_every=0, probe_neighbours=5, probe_train_samples=5000,
-             probe_test_samples=1000, augment='', swd_samples=0, swd_patches=128, swd_dirs=128, swd_repeats=4)
+             probe_test_samples=1000, augment='', swd_samples=0, swd_patches=128, swd_dirs=128, swd_repeats=4,
+             authenticity_samples=0, authenticity_neighbours=3, authenticity_train_samples=50000)
     d.update(over)
     return argparse.Namespace(**d)
 
