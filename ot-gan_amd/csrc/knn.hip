@@ -5,60 +5,41 @@
 //     with d2(a, b) = max(0, (n_a + n_b) - 2 a.b) and n_x = x.x.
 // The distance matrix is never written: as in kid.hip a workgroup of four waves forms a 64 x 64 block of the Gram matrix
 // with the block product of gram64.h (exact fp32 x fp32 products on the fp64 MFMA) and the epilogue differs: a workgroup
-// keeps its 64 query rows, walks the column blocks of its share of the columns, and after each block every lane folds
-// its 8 rows x 2 columns of distances into 8 sorted lists and 8 counters, all in registers (a compare-exchange chain of
-// v_min_f64 / v_max_f64 with static indices: 16 values x KL steps per block and lane against 2048 MFMAs per block and
-// wave at C = 2048).  The lists hold KL = 4 doubles for k <= 4 and 8 otherwise: 8 lists of 8 are 128 registers, which
-// with the 32 of the accumulators leave one workgroup per CU; lists of 4 leave two, as the usual k = 3 wants.  The
-// lists of the 32 lanes that share a row (16 lanes x the 2 waves of a block row) are merged ONCE, after the last column
-// block: an xor tree over the lanes, then LDS over the two waves.
+// keeps its 64 query rows, walks the column blocks of its share of the columns, and after each block every lane offers
+// its 8 rows x 2 columns of distances to the 8 lists and 8 counters it holds.  The selection -- lists, merges over the 32
+// lanes that share a row (16 lanes x the 2 waves of a block row), column split, second launch -- is selectk.h's.
+// Order: doubles ascending, an exchange is v_min_f64 / v_max_f64 (16 values x KL steps per block and lane against 2048
+// MFMAs per block and wave at C = 2048).  Lists of 8 doubles for 8 rows are 128 registers, which with the 32 of the
+// accumulators leave one workgroup per CU; lists of 4 leave two, as the usual k = 3 wants.
+// Masks: a masked element (ragged row, ragged column, the excluded column) is offered as +inf and not counted; rows past
+// the end read the last row (gram64.h).
+// The counts ride along: summed over the lanes beside the tree, over the two waves in LDS, over the splits in the second
+// launch.
 // One bit pattern per pair: a.b depends on (a, b, C) only and a.b == b.a, because every kernel here and in kid.hip runs
 // the one loop of gram64.h (the order of additions: there); the norms are the DIAGONAL of the same block product
-// (knn_norm_kernel), so n_x == x.x of that order and d2(a, a) == 0 exactly; n_a + n_b commutes.  A k-smallest list is a multiset and a count an integer, so the outputs depend neither on the order of the
+// (knn_norm_kernel), so n_x == x.x of that order and d2(a, a) == 0 exactly; n_a + n_b commutes.  Equal distances are
+// interchangeable in a list of values and a count is an integer, so the outputs depend neither on the order of the
 // columns nor on their split over workgroups.
-// Column split: with few query blocks the column blocks are split over blockIdx.y (knn_plan: about 1024 workgroups, at
-// least 4 column blocks each); every (split, row) leaves k doubles and one count in the workspace and a second launch
-// merges the splits of each row -- always, also for one split.  No atomics.  Workspace: the norms of q and y, then
-// [splits][nq][k] doubles, then [splits][nq] counts.
-// Ragged edges: rows past the end read the last row (gram64.h) and are masked where the distances are folded.
+// Workspace: the norms of q and y, then [splits][nq][k] doubles, then [splits][nq] counts.
 #include <limits>
 
 #include "gram64.h"
+#include "selectk.h"
 #include "../../include/otgan.h"
 
 namespace {
 
-constexpr int kKnnMaxK = 8;      // length of the register lists
-constexpr int kKnnMinPer = 4;    // fewest column blocks a split is worth
-constexpr int kKnnGroups = 1024; // workgroups the column split aims at
-
-struct KnnPlan {
-  int nbq, nbc, per, splits;     // query blocks, column blocks, column blocks per split, splits
-};
-
-inline KnnPlan knn_plan(int nq, int ny) {
-  KnnPlan p;
-  p.nbq = (nq + kGramBlock - 1) / kGramBlock;
-  p.nbc = (ny + kGramBlock - 1) / kGramBlock;
-  p.per = p.splits = 0;
-  if (p.nbq == 0 || p.nbc == 0) return p;
-  const int want = (kKnnGroups + p.nbq - 1) / p.nbq;
-  p.per = (p.nbc + want - 1) / want;
-  if (p.per < kKnnMinPer) p.per = kKnnMinPer;
-  p.splits = (p.nbc + p.per - 1) / p.per;
-  return p;
-}
-
-// v into the ascending list, the largest of the KL + 1 falls out
-template <int KL>
-__device__ __forceinline__ void knn_insert(double (&list)[KL], double v) {
-#pragma unroll
-  for (int t = 0; t < KL; ++t) {
-    const double lo = fmin(list[t], v);
-    v = fmax(list[t], v);
-    list[t] = lo;
+// doubles ascending
+struct KnnOrder {
+  typedef double Entry;
+  static __device__ __forceinline__ double none() { return std::numeric_limits<double>::infinity(); }
+  static __device__ __forceinline__ void exchange(double& slot, double& v) {
+    const double lo = fmin(slot, v);
+    v = fmax(slot, v);
+    slot = lo;
   }
-}
+  static __device__ __forceinline__ double shfl_xor(double e, int o) { return __shfl_xor(e, o, 64); }
+};
 
 // grid (blocks of q + blocks of y), 256 threads: norm[i] = x_i . x_i as the diagonal of the block product of 64 rows with
 // themselves -- the bits the distance kernel gets for a row against a copy of itself
@@ -103,7 +84,6 @@ __global__ __launch_bounds__(256, KL <= 4 ? 2 : 1) void knn_block_kernel(int nq,
   const int wi = wave >> 1, wj = wave & 1;
   const int bi = blockIdx.x, nbc = (ny + kGramBlock - 1) / kGramBlock;
   const int jb0 = blockIdx.y * per, jb1 = min(jb0 + per, nbc);
-  const double inf = std::numeric_limits<double>::infinity();
 
   const float* pa[2];
 #pragma unroll
@@ -121,8 +101,7 @@ __global__ __launch_bounds__(256, KL <= 4 ? 2 : 1) void knn_block_kernel(int nq,
     nrow[s] = normq[min(i, nq - 1)];
     selfj[s] = self0 >= 0 ? (long)self0 + i : -1L;          // (no column has number -1)
     count[s] = 0;
-#pragma unroll
-    for (int t = 0; t < KL; ++t) list[s][t] = inf;
+    sel_fill<KnnOrder>(list[s]);
   }
 
   for (int jb = jb0; jb < jb1; ++jb) {
@@ -146,23 +125,18 @@ __global__ __launch_bounds__(256, KL <= 4 ? 2 : 1) void knn_block_kernel(int nq,
       for (int tj = 0; tj < 2; ++tj) {
         const double d2 = fmax(0.0, (nrow[s] + ncol[tj]) - 2.0 * acc[s >> 2][tj][s & 3]);
         const bool counted = rowok[s] && j[tj] < ny && (long)j[tj] != selfj[s];
-        knn_insert(list[s], counted ? d2 : inf);
+        sel_insert<KnnOrder>(list[s], counted ? d2 : KnnOrder::none());
         count[s] += (thresh != nullptr && counted && d2 <= th[tj]) ? 1 : 0;
       }
   }
 
-  // the 16 lanes c of a wave hold different columns of the same 8 rows: xor tree, after which each has the merged list
+  // the 16 lanes c of a wave hold different columns of the same 8 rows
 #pragma unroll
-  for (int s = 0; s < 8; ++s)
+  for (int s = 0; s < 8; ++s) {
+    sel_merge_lanes<KnnOrder>(list[s], 1, 16);
 #pragma unroll
-    for (int o = 1; o < 16; o <<= 1) {
-      double other[KL];
-#pragma unroll
-      for (int t = 0; t < KL; ++t) other[t] = __shfl_xor(list[s][t], o, 64);
-#pragma unroll
-      for (int t = 0; t < KL; ++t) knn_insert(list[s], other[t]);
-      count[s] += __shfl_xor(count[s], o, 64);
-    }
+    for (int o = 1; o < 16; o <<= 1) count[s] += __shfl_xor(count[s], o, 64);
+  }
   if (c == 0) {
 #pragma unroll
     for (int s = 0; s < 8; ++s) {
@@ -176,15 +150,8 @@ __global__ __launch_bounds__(256, KL <= 4 ? 2 : 1) void knn_block_kernel(int nq,
   // the two waves of a block row, one thread per row
   const int i = bi * kGramBlock + tid;
   if (tid < kGramBlock && i < nq) {
-    double m[KL];
-#pragma unroll
-    for (int t = 0; t < KL; ++t) m[t] = wave_list[0][tid][t];
-#pragma unroll
-    for (int t = 0; t < KL; ++t) knn_insert(m, wave_list[1][tid][t]);
     const long at = (long)blockIdx.y * nq + i;
-#pragma unroll
-    for (int t = 0; t < KL; ++t)
-      if (t < k) part[at * k + t] = m[t];
+    sel_merge_waves<KnnOrder>(wave_list[0][tid], wave_list[1][tid], k, part + at * k);
     cnt[at] = wave_cnt[0][tid] + wave_cnt[1][tid];
   }
 }
@@ -195,19 +162,12 @@ __global__ __launch_bounds__(256) void knn_merge_kernel(int nq, int k, int split
                                                         int* __restrict__ inside) {
   const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= nq) return;
-  double m[kKnnMaxK];
-#pragma unroll
-  for (int t = 0; t < kKnnMaxK; ++t) m[t] = std::numeric_limits<double>::infinity();
+  double m[kSelMaxK];
+  sel_merge_splits<KnnOrder>(m, part, i, nq, k, splits);
   int total = 0;
-  for (int s = 0; s < splits; ++s) {
-    const long at = (long)s * nq + i;
+  for (int s = 0; s < splits; ++s) total += cnt[(long)s * nq + i];
 #pragma unroll
-    for (int t = 0; t < kKnnMaxK; ++t)
-      if (t < k) knn_insert(m, part[at * k + t]);
-    total += cnt[at];
-  }
-#pragma unroll
-  for (int t = 0; t < kKnnMaxK; ++t)
+  for (int t = 0; t < kSelMaxK; ++t)
     if (t < k) nearest[i * k + t] = m[t];
   if (inside) inside[i] = total;
 }
@@ -219,8 +179,8 @@ inline size_t knn_norm_doubles(int nq, int ny) { return (size_t)nq + (size_t)ny;
 extern "C" {
 
 size_t otgan_knn_workspace_bytes(int nq, int ny, int k) {
-  if (nq <= 0 || ny <= 0 || k < 0 || k > kKnnMaxK) return 0;
-  const KnnPlan p = knn_plan(nq, ny);
+  if (nq <= 0 || ny <= 0 || k < 0 || k > kSelMaxK) return 0;
+  const SelPlan p = sel_plan(nq, ny, kGramBlock);
   const size_t rows = (size_t)p.splits * (size_t)nq;
   const size_t bytes = (knn_norm_doubles(nq, ny) + rows * (size_t)k) * sizeof(double) + rows * sizeof(int32_t);
   return (bytes + 7) & ~(size_t)7;
@@ -232,7 +192,7 @@ int otgan_knn_f64(int nq, int ny, int C, const float* q, int ldq, const float* y
   OTGAN_CHECK_ARG(nq >= 0 && ny >= 0 && C > 0 && C % 4 == 0 && ldq >= C && ldy >= C && ldq % 4 == 0 && ldy % 4 == 0,
                   "otgan_knn_f64: nq %d >= 0, ny %d >= 0, C %d a positive multiple of 4, ldq %d and ldy %d >= C and "
                   "multiples of 4", nq, ny, C, ldq, ldy);
-  OTGAN_CHECK_ARG(k >= 0 && k <= kKnnMaxK && self0 >= -1, "otgan_knn_f64: k %d in 0 ... %d, self0 %d >= -1", k, kKnnMaxK, self0);
+  OTGAN_CHECK_ARG(k >= 0 && k <= kSelMaxK && self0 >= -1, "otgan_knn_f64: k %d in 0 ... %d, self0 %d >= -1", k, kSelMaxK, self0);
   OTGAN_CHECK_ARG((thresh == nullptr) == (inside == nullptr) || (ny == 0 && !thresh),      // (no column: no threshold to point at)
                   "otgan_knn_f64: thresh and inside go together");
   OTGAN_CHECK_ARG((nearest || k == 0 || nq == 0) && (q || nq == 0) && (y || ny == 0), "otgan_knn_f64: null argument");
@@ -241,7 +201,7 @@ int otgan_knn_f64(int nq, int ny, int C, const float* q, int ldq, const float* y
                       (reinterpret_cast<uintptr_t>(inside) & 3) == 0 && (reinterpret_cast<uintptr_t>(workspace) & 7) == 0,
                   "otgan_knn_f64: misaligned pointer (rows 16 bytes, thresh, nearest and workspace 8, inside 4)");
   if (nq == 0 || (k == 0 && !inside)) return OTGAN_OK;
-  const KnnPlan p = knn_plan(nq, ny);
+  const SelPlan p = sel_plan(nq, ny, kGramBlock);
   if (ny > 0 && (!workspace || workspace_bytes < otgan_knn_workspace_bytes(nq, ny, k))) {
     otgan_set_error("otgan_knn_f64: workspace of %zu bytes, otgan_knn_workspace_bytes(%d, %d, %d) = %zu", workspace_bytes,
                     nq, ny, k, otgan_knn_workspace_bytes(nq, ny, k));
@@ -257,7 +217,7 @@ int otgan_knn_f64(int nq, int ny, int C, const float* q, int ldq, const float* y
     hipLaunchKernelGGL(knn_norm_kernel, dim3(p.nbq + p.nbc), dim3(256), 0, (hipStream_t)stream, nq, ny, C, q, (long)ldq, y,
                        (long)ldy, normq, normy);
     OTGAN_CHECK_LAUNCH("otgan_knn_f64 (norms)");
-    auto kernel = k <= 4 ? knn_block_kernel<4> : knn_block_kernel<kKnnMaxK>;
+    auto kernel = k <= 4 ? knn_block_kernel<4> : knn_block_kernel<kSelMaxK>;
     hipLaunchKernelGGL(kernel, dim3(p.nbq, p.splits), dim3(256), 0, (hipStream_t)stream, nq, ny, C, q, (long)ldq, y,
                        (long)ldy, k, self0, (const double*)normq, (const double*)normy, thresh, p.per, part, cnt);
     OTGAN_CHECK_LAUNCH("otgan_knn_f64");

@@ -3,16 +3,16 @@
 //       index[i][0 .. k) = the columns of the k smallest d(q_i, y_j) = sum_d (q_id - y_jd)^2 over the raw uint8 values,
 //       dist[i][0 .. k)  = those values,
 //     sorted by distance ascending, equal distances by the smaller column first ((-1, -1) where fewer were counted).
-// topk.hip is the model for everything but the product.  Operands: a byte x becomes the int8 x - 128 while it is staged
-// (x ^ 0x80), which changes no difference; with a = q - 128, b = y - 128
+// The selection -- lists, merges, column split, second launch -- is selectk.h's; the product, the score and the order are
+// this file's.  Operands: a byte x becomes the int8 x - 128 while it is staged (x ^ 0x80), which changes no difference;
+// with a = q - 128, b = y - 128
 //       d = |a|^2 + |b|^2 - 2 a.b,
 // a.b from v_mfma_i32_16x16x64_i8 (int32 accumulators), the norms from a pre-pass into the workspace.  Bounds, D <= 49152:
 //   |a.b| and the norms <= D 2^14 <= 805 306 368 < 2^31 -- int32 holds every partial sum, products and sums are EXACT;
 //   d <= D 255^2 <= 3 196 108 800: past int32, inside uint32.  The epilogue adds the three terms in unsigned 32 bits (the true
 //   value is in range, so the wrapped sum is it) and packs (d << 32) | j into one 64-bit key: plain unsigned order on the
-//   key is the pair order above, an insertion step is one 64-bit min and max, and a column occurs once per row, so a list --
-//   and every merge of lists -- is a function of the set of (distance, column) pairs alone: the outputs depend neither on
-//   the visiting order nor on the split over lanes, waves and workgroups, bit for bit, with no tolerance anywhere.
+//   key is the pair order above -- total, since a column occurs once per row -- and an exchange is one 64-bit min and max.
+//   Integers throughout: the outputs are exact, with no tolerance anywhere.
 // A masked element (ragged row, ragged column, the excluded column) is the key ~0: above every real key (d < 2^32 - 1).
 // Tile: a workgroup of four waves (2 x 2) takes 128 queries x 128 columns per block step, K in chunks of 128 bytes through
 // LDS (rows of 144 bytes: the 16 rows a fragment load touches fall on 16 different bank quads), the next chunk in flight in
@@ -24,11 +24,10 @@
 // epilogue is a compare per value.  The A/B lane map (which k a lane's 16 bytes are) does not matter as long as both
 // operands are fetched alike: a dot product is a sum over k in any order, and integer sums are exact.
 // K tail: 16-byte units at or past D are staged as int8 zeros in both operands (D % 16 == 0).
-// The lists of the 8 holders of a query (4 lane groups x the 2 waves of a query half) are merged once, after the last block:
-// xor tree over the lane groups, LDS over the two waves.  Column split as topk.hip; every (split, row) leaves k keys in the
-// workspace and a second launch merges them -- always, also for one split.  No atomics.
+// The holders of a query are 8: 4 lane groups x the 2 waves of a query half.
 // Workspace: [splits][nq][k] uint64 keys, then nq + ny int32 norms (queries first).
 #include "common.h"
+#include "selectk.h"
 #include "../../include/otgan.h"
 #include "../../include/otgan_layers.h"
 
@@ -37,44 +36,24 @@ namespace {
 typedef int i32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned long long u64;
 
-constexpr int kNnMaxK = 8;          // length of the long register lists
 constexpr int kNnTile = 128;        // queries and columns of a block step
 constexpr int kNnChunk = 128;       // bytes of K per staged chunk
 constexpr int kNnPitch = 144;       // LDS row pitch in bytes
-constexpr int kNnMinPer = 4;        // fewest column blocks a split is worth
-constexpr int kNnGroups = 1024;     // workgroups the column split aims at
 constexpr int kNnMaxD = 49152;
-constexpr u64 kNnNone = ~0ull;
 
-struct NnPlan {
-  int nbq, nbc, per, splits;        // query blocks, column blocks, column blocks per split, splits
-};
-
-inline NnPlan nn_plan(int nq, int ny) {
-  NnPlan p;
-  p.nbq = (int)(((long)nq + kNnTile - 1) / kNnTile);
-  p.nbc = (int)(((long)ny + kNnTile - 1) / kNnTile);
-  p.per = p.splits = 0;
-  if (p.nbq == 0 || p.nbc == 0) return p;
-  const int want = (kNnGroups + p.nbq - 1) / p.nbq;
-  p.per = (p.nbc + want - 1) / want;
-  if (p.per < kNnMinPer) p.per = kNnMinPer;
-  p.splits = (p.nbc + p.per - 1) / p.per;
-  return p;
-}
-
-inline size_t nn_key_slots(const NnPlan& p, int nq, int k) { return (size_t)p.splits * (size_t)nq * (size_t)k; }
-
-// v into the sorted list, the largest of the KL + 1 falls out
-template <int KL>
-__device__ __forceinline__ void nn_insert(u64 (&l)[KL], u64 v) {
-#pragma unroll
-  for (int t = 0; t < KL; ++t) {
-    const u64 a = l[t];
-    l[t] = a < v ? a : v;
+// packed (distance << 32) | column keys ascending
+struct NnOrder {
+  typedef u64 Entry;
+  static __device__ __forceinline__ u64 none() { return ~0ull; }
+  static __device__ __forceinline__ void exchange(u64& slot, u64& v) {
+    const u64 a = slot;
+    slot = a < v ? a : v;
     v = a < v ? v : a;
   }
-}
+  static __device__ __forceinline__ u64 shfl_xor(u64 e, int o) { return __shfl_xor(e, o, 64); }
+};
+
+inline size_t nn_key_slots(const SelPlan& p, int nq, int k) { return (size_t)p.splits * (size_t)nq * (size_t)k; }
 
 // norm[r] = sum_d (x_rd - 128)^2, one wave per row and trip of the grid, 16 bytes per lane and trip of the row
 __global__ __launch_bounds__(256) void nn_norm_kernel(long rows, int D, const uint8_t* __restrict__ x, long ld, int* __restrict__ norm) {
@@ -127,8 +106,8 @@ __global__ __launch_bounds__(256, 2) void nn_block_kernel(int nq, int ny, int D,
     lds_at[e] = row * kNnPitch + ku;
   }
 
-  // slot b of this lane is query 64 wq + 16 b + c of the block; the guards as ints (topk.hip): the columns of a query end
-  // at jend (0 past nq: none is counted), selfj is the excluded one (~0: none).  Row and column numbers are unsigned here:
+  // slot b of this lane is query 64 wq + 16 b + c of the block; the guards as two ints per query: its columns end at jend
+  // (0 past nq: none is counted), selfj is the excluded one (~0: none).  Row and column numbers are unsigned here:
   // the last block of ny = 2^31 - 2 columns runs past 2^31
   u64 lst[4][KL];
   unsigned selfj[4], jend[4], qn[4];
@@ -138,8 +117,7 @@ __global__ __launch_bounds__(256, 2) void nn_block_kernel(int nq, int ny, int D,
     jend[b] = i < (unsigned)nq ? (unsigned)ny : 0u;
     qn[b] = i < (unsigned)nq ? (unsigned)qnorm[i] : 0u;
     selfj[b] = (self0 >= 0 && (long)self0 + (long)i < ny) ? (unsigned)self0 + i : ~0u;
-#pragma unroll
-    for (int t = 0; t < KL; ++t) lst[b][t] = kNnNone;
+    sel_fill<NnOrder>(lst[b]);
   }
 
   for (int jb = jb0; jb < jb1; ++jb) {
@@ -207,23 +185,15 @@ __global__ __launch_bounds__(256, 2) void nn_block_kernel(int nq, int ny, int D,
         for (int b = 0; b < 4; ++b) {
           const unsigned d = qn[b] + yn - 2u * (unsigned)acc[a][b][r];
           const bool counted = j < jend[b] && j != selfj[b];
-          const u64 key = counted ? (((u64)d << 32) | j) : kNnNone;
-          if (key < lst[b][KL - 1]) nn_insert(lst[b], key);
+          const u64 key = counted ? (((u64)d << 32) | j) : NnOrder::none();
+          if (key < lst[b][KL - 1]) sel_insert<NnOrder>(lst[b], key);
         }
       }
   }
 
-  // the 4 lane groups of a wave hold different columns of the same queries: xor tree (a loop: see topk.hip)
+  // the 4 lane groups of a wave hold different columns of the same queries
 #pragma unroll
-  for (int b = 0; b < 4; ++b)
-#pragma unroll 1
-    for (int o = 16; o < 64; o <<= 1) {
-      u64 other[KL];
-#pragma unroll
-      for (int t = 0; t < KL; ++t) other[t] = __shfl_xor(lst[b][t], o, 64);
-#pragma unroll
-      for (int t = 0; t < KL; ++t) nn_insert(lst[b], other[t]);
-    }
+  for (int b = 0; b < 4; ++b) sel_merge_lanes<NnOrder>(lst[b], 16, 64);
   if (g == 0) {
 #pragma unroll
     for (int b = 0; b < 4; ++b)
@@ -233,17 +203,8 @@ __global__ __launch_bounds__(256, 2) void nn_block_kernel(int nq, int ny, int D,
   __syncthreads();
   // the two waves of a query half, one thread per query
   const unsigned i = (unsigned)bi * kNnTile + tid;
-  if (tid < kNnTile && i < (unsigned)nq) {
-    u64 m[KL];
-#pragma unroll
-    for (int t = 0; t < KL; ++t) m[t] = wave_keys[0][tid][t];
-#pragma unroll
-    for (int t = 0; t < KL; ++t) nn_insert(m, wave_keys[1][tid][t]);
-    const long at = ((long)blockIdx.y * nq + i) * k;
-#pragma unroll
-    for (int t = 0; t < KL; ++t)
-      if (t < k) part[at + t] = m[t];
-  }
+  if (tid < kNnTile && i < (unsigned)nq)
+    sel_merge_waves<NnOrder>(wave_keys[0][tid], wave_keys[1][tid], k, part + ((long)blockIdx.y * nq + i) * k);
 }
 
 // one thread per query row: the first k keys of its splits' lists (splits == 0: every slot empty); an empty slot leaves
@@ -252,19 +213,12 @@ __global__ __launch_bounds__(256) void nn_merge_kernel(int nq, int k, int splits
                                                        int* __restrict__ index, long long* __restrict__ dist) {
   const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= nq) return;
-  u64 m[kNnMaxK];
+  u64 m[kSelMaxK];
+  sel_merge_splits<NnOrder>(m, part, i, nq, k, splits);
 #pragma unroll
-  for (int t = 0; t < kNnMaxK; ++t) m[t] = kNnNone;
-  for (int s = 0; s < splits; ++s) {
-    const long at = ((long)s * nq + i) * k;
-#pragma unroll
-    for (int t = 0; t < kNnMaxK; ++t)
-      if (t < k) nn_insert(m, part[at + t]);
-  }
-#pragma unroll
-  for (int t = 0; t < kNnMaxK; ++t)
+  for (int t = 0; t < kSelMaxK; ++t)
     if (t < k) {
-      const bool none = m[t] == kNnNone;
+      const bool none = m[t] == NnOrder::none();
       index[i * k + t] = none ? -1 : (int)(unsigned)(m[t] & 0xffffffffull);
       dist[i * k + t] = none ? -1ll : (long long)(m[t] >> 32);
     }
@@ -277,8 +231,8 @@ inline size_t nn_norm_bytes(int nq, int ny) { return ((((size_t)nq + (size_t)ny)
 extern "C" {
 
 size_t otgan_nn_u8_workspace_bytes(int nq, int ny, int k) {
-  if (nq <= 0 || ny <= 0 || k < 1 || k > kNnMaxK) return 0;
-  return nn_key_slots(nn_plan(nq, ny), nq, k) * sizeof(u64) + nn_norm_bytes(nq, ny);
+  if (nq <= 0 || ny <= 0 || k < 1 || k > kSelMaxK) return 0;
+  return nn_key_slots(sel_plan(nq, ny, kNnTile), nq, k) * sizeof(u64) + nn_norm_bytes(nq, ny);
 }
 
 int otgan_nn_u8(int nq, int ny, int D, const uint8_t* q, long ldq, const uint8_t* y, long ldy, int k, int self0,
@@ -287,14 +241,14 @@ int otgan_nn_u8(int nq, int ny, int D, const uint8_t* q, long ldq, const uint8_t
   OTGAN_CHECK_ARG(D >= 16 && D <= kNnMaxD && D % 16 == 0, "otgan_nn_u8: D %d a multiple of 16 in 16 ... %d", D, kNnMaxD);
   OTGAN_CHECK_ARG(ldq >= D && ldy >= D && ldq % 16 == 0 && ldy % 16 == 0,
                   "otgan_nn_u8: ldq %ld and ldy %ld >= D %d and multiples of 16", ldq, ldy, D);
-  OTGAN_CHECK_ARG(k >= 1 && k <= kNnMaxK && self0 >= -1, "otgan_nn_u8: k %d in 1 ... %d, self0 %d >= -1", k, kNnMaxK, self0);
+  OTGAN_CHECK_ARG(k >= 1 && k <= kSelMaxK && self0 >= -1, "otgan_nn_u8: k %d in 1 ... %d, self0 %d >= -1", k, kSelMaxK, self0);
   OTGAN_CHECK_ARG(((index && dist) || nq == 0) && (q || nq == 0) && (y || ny == 0), "otgan_nn_u8: null argument");
   OTGAN_CHECK_ARG((reinterpret_cast<uintptr_t>(q) & 15) == 0 && (reinterpret_cast<uintptr_t>(y) & 15) == 0 &&
                       (reinterpret_cast<uintptr_t>(index) & 3) == 0 && (reinterpret_cast<uintptr_t>(dist) & 7) == 0 &&
                       (reinterpret_cast<uintptr_t>(workspace) & 7) == 0,
                   "otgan_nn_u8: misaligned pointer (rows 16 bytes, dist and workspace 8, index 4)");
   if (nq == 0) return OTGAN_OK;
-  const NnPlan p = nn_plan(nq, ny);
+  const SelPlan p = sel_plan(nq, ny, kNnTile);
   if (ny > 0 && (!workspace || workspace_bytes < otgan_nn_u8_workspace_bytes(nq, ny, k))) {
     otgan_set_error("otgan_nn_u8: workspace of %zu bytes, otgan_nn_u8_workspace_bytes(%d, %d, %d) = %zu", workspace_bytes, nq,
                     ny, k, otgan_nn_u8_workspace_bytes(nq, ny, k));
@@ -310,7 +264,7 @@ int otgan_nn_u8(int nq, int ny, int D, const uint8_t* q, long ldq, const uint8_t
     OTGAN_CHECK_LAUNCH("otgan_nn_u8 (query norms)");
     hipLaunchKernelGGL(nn_norm_kernel, dim3(nn_norm_grid(ny)), dim3(256), 0, st, (long)ny, D, y, ldy, ynorm);
     OTGAN_CHECK_LAUNCH("otgan_nn_u8 (column norms)");
-    auto kernel = k <= 4 ? nn_block_kernel<4> : nn_block_kernel<kNnMaxK>;
+    auto kernel = k <= 4 ? nn_block_kernel<4> : nn_block_kernel<kSelMaxK>;
     hipLaunchKernelGGL(kernel, dim3(p.nbq, p.splits), dim3(256), 0, st, nq, ny, D, q, ldq, y, ldy, k, self0, p.per,
                        (const int*)qnorm, (const int*)ynorm, part);
     OTGAN_CHECK_LAUNCH("otgan_nn_u8");

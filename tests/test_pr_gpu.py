@@ -53,7 +53,7 @@ def _sets(seed, ng, nr, C, equal_noise=False):
 # than one column block per workgroup (65 x 130), a column split with few rows (5 x 1500: 6 splits of 4 blocks), both
 # list lengths of the kernel (k <= 4 and k > 4), and the full width with two splits of 4 + 1 blocks (300 x 257 x 2048)
 SHAPES = [(1, 2, 4, 1), (3, 3, 4, 3), (7, 9, 40, 3), (16, 17, 40, 3), (17, 16, 40, 3), (33, 30, 100, 3), (63, 64, 40, 1),
-          (64, 65, 40, 8), (65, 130, 40, 5), (5, 1500, 40, 3), (300, 257, 2048, 3)]
+          (64, 65, 40, 8), (65, 130, 40, 5), (5, 1500, 40, 3), (70, 600, 40, 8), (300, 257, 2048, 3)]
 
 
 @functools.lru_cache(maxsize=None)
