@@ -1,7 +1,10 @@
 """The calls that pin the three convolution passes (otgan_conv2d_fwd_pf_f32, otgan_conv2d_dgrad_pf_f32, otgan_conv2d_wgrad_f32)
 to every kernel route of csrc/conv.hip, and the route predicates restated in Python.  tests/test_conv_routes_cpu.py keeps the
 table on the routes it claims and compares the restatement with the library's host queries; tests/test_conv_routes_gpu.py runs
-the table through the C ABI.  No GPU and no library is needed to import this module.
+the table through the C ABI; tests/test_conv_sparse_gpu.py runs its non-Winograd routes a second time, on the sparse inputs of
+tests/conv_sparse.py with one error bar per output element (worst error / bar per route family: in its docstring), and
+tests/test_amax_bounds_gpu.py its two-fp16-piece routes under amax records above the exact maximum.  No GPU and no library is
+needed to import this module.
 
 The three bodies (conv2d_fwd_body, conv2d_dgrad_body, otgan_conv2d_wgrad_f32) choose among about thirty kernels from the
 descriptor, the alignment of every pointer, the pitches ldx / ldy / y_coff / lddx, the channel map, the workspace, `filters` and
