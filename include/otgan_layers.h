@@ -697,4 +697,42 @@ int otgan_swd_project_u8(const uint8_t* img, long n, int S, const int32_t* pos, 
                          const float* inv_std, const float* dirs, int nd, float* proj, long ldp, void* stream);
 int otgan_swd_row_l1_f64(const float* a, long lda, const float* b, long ldb, int rows, long m, double* out, void* stream);
 
+/* ---------------------------------------------------------------------------------------
+ * Health of a training step (--health_every; utils/health.py; csrc/health.hip): gradient, parameter and update statistics of
+ * every variable in one pass, and the marginal residuals of Sinkhorn plans.  Nothing the reference computes.
+ *
+ * otgan_tensor_health_f32: nseg tensors ("segments") in one call.  x and ref are HOST arrays of nseg DEVICE pointers (fp32,
+ *   4-byte aligned, any alignment beyond that), as otgan_cost_matrix_batched_f32 takes them; ref, or any of its entries, may be
+ *   null; n is a HOST array of element counts, 0 allowed (x[i] is then not read and may be null).  Any nseg >= 0: segments go out
+ *   in launches of OTGAN_HEALTH_MAX_SEGMENTS.
+ *   out: double [nseg][6] (device), per segment, over the FINITE elements of x (a non-finite x_k enters none of slots 0 - 4):
+ *     0  sum x^2          1  max |x|
+ *     2  sum (x - ref)^2  3  max |x - ref|      over the elements where ref is finite too; both 0 when ref is null
+ *     4  the count of exact zeros (+0 and -0)   5  the count of non-finite elements (inf, NaN) of x
+ *   hist: unsigned 64-bit [nseg][256] (device), per segment one count per finite non-zero element, in the bucket of its biased
+ *     fp32 exponent (bits 30 ... 23 of |x|): denormals in bucket 0, bucket 255 stays empty.  sum(hist) + out[4] + out[5] == n.
+ *   Arithmetic: x^2 is exact in fp64; d = (double)x - (double)ref and d * d are one IEEE fp64 operation each; the sums are fp64
+ *   in a fixed order: a segment is cut into chunks of OTGAN_HEALTH_CHUNK elements counted from its own first element, a chunk is
+ *   summed as thread t of 256 = elements t, t + 256, ... in order, then a 64-lane butterfly, then the four wave sums as
+ *   (w0 + w1) + (w2 + w3); the chunks' partial results go to the workspace and a finishing launch adds them the same way.  No
+ *   float atomics (the histogram uses integer adds).  A segment's 6 + 256 numbers are therefore the same bits alone or among
+ *   other segments, at any pointer alignment, and from call to call.  One pass over x and ref: 16-byte loads on the 16-byte
+ *   aligned body of a chunk, scalar loads on its head and tail.
+ *   workspace: otgan_tensor_health_workspace_bytes(n, nseg) bytes, 8-byte aligned; OTGAN_ERR_WORKSPACE when smaller.
+ *
+ * otgan_plan_marginals_f32: plan fp32 [P][n][ldp] (ldp >= m; rectangular and pitched plans) -> out double [P][4] (device):
+ *     0  max_i |r_i - 1|   1  mean_i |r_i - 1|   2  max_j |c_j - n/m|   3  mean_j |c_j - n/m|
+ *   with r_i = sum_j plan[p][i][j] and c_j = sum_i plan[p][i][j] taken in fp64 in a fixed order that depends on (n, m) only; no
+ *   atomics.  n, m >= 1.  workspace: otgan_plan_marginals_workspace_bytes(P, n, m) bytes, 8-byte aligned.
+ * An argument error returns nonzero with a message before any launch.
+ */
+#define OTGAN_HEALTH_CHUNK 2048
+#define OTGAN_HEALTH_MAX_SEGMENTS 64
+size_t otgan_tensor_health_workspace_bytes(const long* n, int nseg);
+int otgan_tensor_health_f32(const float* const* x, const float* const* ref, const long* n, int nseg, double* out,
+                            unsigned long long* hist, void* workspace, size_t workspace_bytes, void* stream);
+size_t otgan_plan_marginals_workspace_bytes(int P, int n, int m);
+int otgan_plan_marginals_f32(const float* plan, int P, int n, int m, long ldp, double* out, void* workspace,
+                             size_t workspace_bytes, void* stream);
+
 #endif /* OTGAN_LAYERS_H */

@@ -143,4 +143,8 @@ SIGNATURES = {
     "otgan_swd_channel_stats_u8": (c_int, [c_fp, c_long, c_int, c_fp, c_int, c_fp, c_fp, c_fp, c_size_t, c_fp]),
     "otgan_swd_project_u8": (c_int, [c_fp, c_long, c_int, c_fp, c_int, c_int, c_fp, c_fp, c_fp, c_int, c_fp, c_long, c_fp]),
     "otgan_swd_row_l1_f64": (c_int, [c_fp, c_long, c_fp, c_long, c_int, c_long, c_fp, c_fp]),
+    "otgan_tensor_health_workspace_bytes": (c_size_t, [c_fp, c_int]),
+    "otgan_tensor_health_f32": (c_int, [c_fp, c_fp, c_fp, c_int, c_fp, c_fp, c_fp, c_size_t, c_fp]),
+    "otgan_plan_marginals_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "otgan_plan_marginals_f32": (c_int, [c_fp, c_int, c_int, c_int, c_long, c_fp, c_fp, c_size_t, c_fp]),
 }

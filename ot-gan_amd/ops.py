@@ -2071,3 +2071,77 @@ def nn_u8(q, y, k, self0=-1):
                                  y.stride(0) if ny > 1 else D, k, self0, index.data_ptr(), dist.data_ptr(), ws.data_ptr(),
                                  ws.numel(), _lib.stream_ptr()), "nn_u8")
     return index, dist
+
+
+HEALTH_CHUNK, HEALTH_MAX_SEGMENTS = 2048, 64      # otgan_layers.h: OTGAN_HEALTH_CHUNK, OTGAN_HEALTH_MAX_SEGMENTS
+
+
+def tensor_health(tensors, refs=None):
+    """(out float64 [nseg, 6], hist int64 [nseg, 256]) of a list of float32 CUDA tensors, one segment each
+    (otgan_tensor_health_f32): per segment sum x^2, max |x|, sum (x - ref)^2, max |x - ref|, the count of exact zeros and the
+    count of non-finite elements, and one count per finite non-zero element in the bucket of its biased fp32 exponent.  `refs`:
+    None, or a list as long as `tensors` of tensors of the same sizes, entries may be None (slots 2 and 3 are then 0).  The
+    results of a segment do not depend on the other segments, on alignment or on the call.  No host synchronisation."""
+    tensors = list(tensors)
+    refs = None if refs is None else list(refs)
+    if refs is not None and len(refs) != len(tensors):
+        raise ValueError("tensor_health: %d tensors and %d refs" % (len(tensors), len(refs)))
+    _need_cuda(*tensors)
+    if refs is not None:
+        _need_cuda(*refs)
+    if not tensors:
+        raise ValueError("tensor_health: no tensor (the device of the result is the tensors')")
+    dev = tensors[0].device
+    xs, rs = [], []
+    for i, t in enumerate(tensors):
+        r = None if refs is None else refs[i]
+        for u, what in ((t, "tensor"), (r, "ref")):
+            if u is not None and not (torch.is_tensor(u) and u.dtype == torch.float32 and u.device == dev):
+                raise ValueError("tensor_health: %s %d must be a float32 tensor on %s" % (what, i, dev))
+        if r is not None and r.numel() != t.numel():
+            raise ValueError("tensor_health: tensor %d has %d elements, its ref %d" % (i, t.numel(), r.numel()))
+        xs.append(t.detach().contiguous())
+        rs.append(None if r is None else r.detach().contiguous())
+    nseg = len(xs)
+    out = torch.empty(nseg, 6, dtype=torch.float64, device=dev)
+    hist = torch.empty(nseg, 256, dtype=torch.int64, device=dev)
+    arr = ctypes.c_void_p * nseg
+    X = arr(*[x.data_ptr() if x.numel() else None for x in xs])
+    R = None if refs is None else arr(*[r.data_ptr() if r is not None and r.numel() else None for r in rs])
+    n = (ctypes.c_long * nseg)(*[x.numel() for x in xs])
+    L = _lib.lib()
+    with torch.cuda.device(dev):
+        nbytes = L.otgan_tensor_health_workspace_bytes(ctypes.cast(n, ctypes.c_void_p), nseg)
+        ws = workspace(nbytes, dev)
+        _lib.check(L.otgan_tensor_health_f32(ctypes.cast(X, ctypes.c_void_p), None if R is None else ctypes.cast(R, ctypes.c_void_p),
+                                             ctypes.cast(n, ctypes.c_void_p), nseg, out.data_ptr(), hist.data_ptr(), ws.data_ptr(),
+                                             ws.numel(), _lib.stream_ptr()), "tensor_health")
+    return out, hist
+
+
+def plan_marginals(plan):
+    """float64 [P, 4]: max_i |r_i - 1|, mean_i |r_i - 1|, max_j |c_j - n/m|, mean_j |c_j - n/m| of the row sums r and column
+    sums c of float32 CUDA plans [P, n, m] (or [n, m]) with unit column stride; a row pitch above m is passed on
+    (otgan_plan_marginals_f32).  No host synchronisation."""
+    _need_cuda(plan)
+    if not (torch.is_tensor(plan) and plan.dtype == torch.float32 and plan.dim() in (2, 3)):
+        raise ValueError("plan_marginals takes float32 plans [P, n, m] or [n, m]")
+    if plan.dim() == 2:
+        plan = plan.unsqueeze(0)
+    P, n, m = plan.shape
+    if n < 1 or m < 1:
+        raise ValueError("plan_marginals: empty plans %s" % (tuple(plan.shape),))
+    ldp = plan.stride(1) if n > 1 else m
+    if not ((m == 1 or plan.stride(2) == 1) and ldp >= m and (P == 1 or plan.stride(0) == n * ldp)):
+        plan = plan.contiguous()
+        ldp = m
+    out = torch.empty(P, 4, dtype=torch.float64, device=plan.device)
+    if P == 0:
+        return out
+    L = _lib.lib()
+    with torch.cuda.device(plan.device):
+        nbytes = L.otgan_plan_marginals_workspace_bytes(P, n, m)
+        ws = workspace(nbytes, plan.device)
+        _lib.check(L.otgan_plan_marginals_f32(plan.data_ptr(), P, n, m, ldp, out.data_ptr(), ws.data_ptr(), ws.numel(),
+                                              _lib.stream_ptr()), "plan_marginals")
+    return out

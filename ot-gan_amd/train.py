@@ -33,7 +33,11 @@ Laplacian-pyramid level between generated and training images, Karras et al. 201
 --authenticity_samples / --authenticity_neighbours / --authenticity_train_samples (utils/authenticity.py: is the generator
 copying the training set?  Exact pixel-space nearest training images of generated samples on the int8 matrix pipe, the
 authenticity score of Alaa et al. 2022 beside a held-out baseline, and nn_sample<epoch>.png: the samples nearest to the
-training set, each beside its nearest training images; same cadence, same fixed samples as --swd_samples).
+training set, each beside its nearest training images; same cadence, same fixed samples as --swd_samples),
+--health_every N (utils/health.py: every N steps, and at the first later step of the other kind, one JSON line in
+<save_dir>/health.jsonl -- gradient, parameter and update norms per variable, the share of every gradient below the 11 and 22
+bits of the split-precision engine, the marginal residuals of the step's Sinkhorn plans -- and one `health:` line per epoch;
+training is the same bit for bit; non-finite gradients are written and then raised before the optimiser runs).
 
 Checkpoints (`<save_dir>/med_gan_params-<epoch>`, the reference's naming, train.py:275-277) are torch pickles
 of {variable name: tensor} plus optimiser moments / step count and EMA shadows (which the reference's
@@ -157,6 +161,11 @@ def build_parser():
                    help='nearest training images shown per sample on the sheet (1 ... 8); the score uses the first')
     p.add_argument('--authenticity_train_samples', type=int, default=50000,
                    help='training images that are searched: the first N')
+    p.add_argument('--health_every', type=int, default=0,
+                   help='every this many steps (and at the first later step of the other kind) append one JSON line to '
+                        '<save_dir>/health.jsonl: gradient, parameter and update norms per variable, the share of every gradient '
+                        'below the 11 and 22 bits of the split-precision engine, and the marginal residuals of the Sinkhorn plans '
+                        '(utils/health.py); one summary line per epoch.  Training is the same bit for bit.  0 = off')
     return p
 
 
@@ -569,6 +578,8 @@ def main(argv=None, self_launch=False):
             authenticity.check_neighbours(args.authenticity_neighbours)
         except ValueError as e:
             raise ValueError("--authenticity_neighbours: %s" % e) from None
+    from .utils import health
+    health.check_every(args.health_every)
     from . import parallel
     from .trainer import OTGAN
     if not parallel.launched() and (self_launch or args.ranks):
@@ -622,6 +633,14 @@ def main(argv=None, self_launch=False):
         sd = torch.load(os.path.join(args.save_dir, args.model_name), map_location='cpu')
         model.load_state_dict(sd)
         current_epoch = int(args.model_name[args.model_name.rfind('-') + 1:])
+    health_state = {"epoch": current_epoch, "gen": None, "disc": None}      # the last reported pair of steps
+    if args.health_every > 0:
+        def health_sink(record):
+            record["epoch"] = health_state["epoch"]
+            health_state[record["kind"]] = record
+            if rank == 0:
+                health.append(os.path.join(args.save_dir, 'health.jsonl'), record)
+        model.health_sink = health_sink
     if rank == 0:
         print('starting training')
     mean_dist_gen, mean_dist_disc = [], []
@@ -644,6 +663,7 @@ def main(argv=None, self_launch=False):
     total = 0
     for epoch in range(current_epoch, 1000000):
         begin = time.time()
+        health_state["epoch"] = epoch
         inds = np.random.permutation(trainx.shape[0])              # same seed on every rank
         if on_device:
             trainx.set_permutation(inds)
@@ -688,6 +708,8 @@ def main(argv=None, self_launch=False):
             print("Iteration %d, time = %ds, train distance before gen = %.6f, train distance before disc = %.6f, "
                   "avg matching entropy = %.6f" % (epoch, time.time() - begin, mean_dist_gen[-1],
                                                    mean_dist_disc[-1], f(ent)))          # train.py:231
+            if args.health_every > 0 and (health_state["gen"] or health_state["disc"]):
+                print(health.summary_line(health_state))
             save_tile_png(model.sample(100), os.path.join(args.save_dir, 'sample%d.png' % epoch))
             save_tile_png(model.sample(100, ema=True), os.path.join(args.save_dir, 'ema_sample%d.png' % epoch))
             if (epoch + 1) % args.save_every == 0 and epoch != current_epoch:                          # train.py:275-277

@@ -8,6 +8,7 @@ import torch
 
 from . import parallel
 from .utils import augment, matching, nn
+from .utils import health as _health
 
 
 def _lib_prof_on():
@@ -121,6 +122,10 @@ class OTGAN:
         self.num_features = f.shape[-1]
         # one flat buffer per network: optimiser / EMA / gradient all-reduce act on it in one go
         groups = (self.discriminator.flatten(), self.generator.flatten())
+        self._groups = {"disc": groups[0], "gen": groups[1]}
+        # --health_every N: gradient, update and Sinkhorn statistics of every N-th step and its partner of the other kind
+        # (utils/health.py; _step_reported below).  0 = off: step() takes the branch it always took
+        self.health_every = _health.check_every(getattr(args, "health_every", 0) or 0)
         if ddi and self.world > 1:
             # the data-dependent pass draws the generator's latent from the per-rank RNG stream (train.py seeds
             # seed + rank), so every rank computed its own g / b statistics: the replicas would start different and
@@ -310,7 +315,10 @@ class OTGAN:
         phase = self.step_counter % period
         kind = "disc" if phase == 0 else "gen"
         self._throttle()
-        if self.graphs is not None and noise is None and aug is None and apply_updates:
+        # a reported step (--health_every) runs its eager body: replayed graphs and eager steps interleave bit for bit
+        # (tests/test_step_graph_interleave_gpu.py)
+        report = self.health_every > 0 and apply_updates and _health.due(self.step_counter, self.health_every, period)
+        if self.graphs is not None and noise is None and aug is None and apply_updates and not report:
             done = self.graphs.run(x_data, phase)
             if done is not None:
                 self.last = done
@@ -318,8 +326,12 @@ class OTGAN:
                 return self.last
         from . import ops
         ops.SIDE_STREAM = self._side_stream if self.fork_wgrad else None
+        record = None
         try:
-            dist, ent, grads = self._step_body(x_data, kind, noise, apply_updates, aug)
+            if report:
+                dist, ent, grads, record = self._step_reported(x_data, kind, noise, aug)
+            else:
+                dist, ent, grads = self._step_body(x_data, kind, noise, apply_updates, aug)
         finally:
             ops.SIDE_STREAM = None
         self._mark_step_end()
@@ -330,7 +342,91 @@ class OTGAN:
         self.last = {"kind": kind, "distance": dist, "entropy": ent}      # device scalars, no sync
         if not apply_updates:
             self.last["grads"] = grads
+        if record is not None:
+            self.last["health"] = record
         return self.last
+
+    # ---------------------------------------------------------------- --health_every (utils/health.py)
+    health_sink = None      # callable(record), called once per reported step before anything can raise (train.main: the file)
+
+    def _step_reported(self, x_data, kind, noise, aug):
+        """A reported step: the launches of the eager step in the eager step's order -- `_step_body` up to the summed
+        gradients, then `_optimise` -- with the health passes between and after them -> (distance, entropy, gradients, record).
+        The passes read; they draw no random number and write nothing the step reads, so training does not move.  Synchronises.
+        Non-finite gradients: the record goes to `health_sink`, then a FloatingPointError names the variables and the optimiser
+        has not run.  The gradients are the cross-rank sums and, in the global matching scope, the problems are the same on
+        every rank: every rank computes the same record (and raises alike), rank 0 is the one whose sink writes it."""
+        from . import ops
+        a = self.args
+        seen = {}
+
+        def recording(name, keep):      # shadow a method of this step's matching for the length of the body
+            inner = getattr(OTGAN, name)
+
+            def call(*args, **kw):
+                out = inner(self, *args, **kw)
+                seen[name] = keep(args, out)
+                return out
+            setattr(self, name, call)
+        recording("_match", lambda args, out: (args[0], args[1]))
+        for name in ("_sharded_log_kernels", "_sharded_single_log_kernels", "_gather_slices"):
+            recording(name, lambda args, out: out)
+        try:
+            dist, ent, grads = self._step_body(x_data, kind, noise, False, aug)
+        finally:
+            for name in ("_match", "_sharded_log_kernels", "_sharded_single_log_kernels", "_gather_slices"):
+                delattr(self, name)
+        critic = kind == "disc"
+        params = self.disc_params if critic else self.gen_params
+        names = list((self.discriminator if critic else self.generator).named_variables())
+        g_out, g_hist = ops.tensor_health(grads)
+        marg, problems = self._plan_health(seen)
+        g_out, g_hist = g_out.cpu().numpy(), g_hist.cpu().numpy()
+        sink = None if marg is None else _health.sinkhorn_block(marg.cpu().numpy(), a.nr_sinkhorn_iter, a.sinkhorn_lambda, problems)
+        scal = dict(distance=float(dist), entropy=float(ent), sinkhorn=sink)
+        if g_out[:, 5].any():
+            record = _health.collect(self.step_counter, kind, names, g_out, g_hist, None, **scal)
+            self.last = {"kind": kind, "distance": dist, "entropy": ent, "health": record}
+            if self.health_sink is not None:
+                self.health_sink(record)
+            raise FloatingPointError("non-finite gradients in %s step %d, before the optimiser: %s"
+                                     % ("critic" if critic else "generator", self.step_counter,
+                                        ", ".join(_health.nonfinite_variables(record))))
+        group = self._groups[kind]
+        before = group.views_of(group.flat.clone())
+        self._optimise(self.disc_optimizer if critic else self.gen_optimizer, grads,
+                       -a.learning_rate_disc if critic else a.learning_rate_gen, critic=critic)
+        p_out, _ = ops.tensor_health(params, refs=[before[id(p)] for p in params])
+        record = _health.collect(self.step_counter, kind, names, g_out, g_hist, p_out.cpu().numpy(), **scal)
+        if self.health_sink is not None:
+            self.health_sink(record)
+        return dist, ent, grads, record
+
+    def _plan_health(self, seen):
+        """(ops.plan_marginals of the plans of this step's matching problems [P, 4], their names in the reference's order):
+        the step's log-kernels -- gathered ones where the step exchanged them, else made from its features by the staged
+        matching.cost_log_kernels -- solved once more by matching.sinkhorn_plans with the step's lambda and sweep count and, for
+        --single_batch, its diagonal terms.  (None, None) with --no_sinkhorn."""
+        from . import ops
+        a = self.args
+        if a.no_sinkhorn:
+            return None, None
+        lam = a.sinkhorn_lambda
+        if "_gather_slices" in seen:
+            K = assemble_log_kernels(seen["_gather_slices"], self.world)
+        elif "_sharded_log_kernels" in seen or "_sharded_single_log_kernels" in seen:
+            K = seen.get("_sharded_log_kernels", seen.get("_sharded_single_log_kernels"))
+        else:
+            f_gen, f_dat = (f.detach().float().contiguous() for f in seen["_match"])
+            if a.single_batch:
+                K = matching.cost_log_kernels([f_gen, f_dat, f_gen], [f_gen, f_dat, f_dat], lam)
+                K = assemble_single_log_kernels(K.unsqueeze(0), lam)
+            else:
+                N = f_gen.shape[0] // 2
+                a1, a2, b1, b2 = f_gen[:N], f_gen[N:], f_dat[:N], f_dat[N:]
+                K = matching.cost_log_kernels([a1, b2, a1, a1, a2, a2], [a2, b1, b1, b2, b1, b2], lam)
+        plans = matching.sinkhorn_plans(K, lam, a.nr_sinkhorn_iter)
+        return ops.plan_marginals(plans), (_health.SINGLE_BATCH_PROBLEMS if a.single_batch else _health.TWO_BATCH_PROBLEMS)
 
     # The host never gets more than `_max_ahead` steps ahead of the device (default 2; 0: unbounded).  With
     # two streams a tensor that the other stream has used (record_stream) returns to torch's caching allocator only once
@@ -837,7 +933,7 @@ def default_args(**over):
              data_on_device=False, kid_subsets=0, kid_subset_size=1000, kid_real_samples=0,
              pr_neighbours=0, pr_real_samples=0, probe_every=0, probe_neighbours=5, probe_train_samples=5000,
              probe_test_samples=1000, augment='', swd_samples=0, swd_patches=128, swd_dirs=128, swd_repeats=4,
-             authenticity_samples=0, authenticity_neighbours=3, authenticity_train_samples=50000)
+             authenticity_samples=0, authenticity_neighbours=3, authenticity_train_samples=50000, health_every=0)
     d.update(over)
     return argparse.Namespace(**d)
 

@@ -193,6 +193,26 @@ def cost_log_kernels(xs, ys, sinkhorn_lambda, cost_kind=COST_COSINE):
     return K
 
 
+def sinkhorn_plans(log_kernels, sinkhorn_lambda, nr_sinkhorn_iter):
+    """The plans [P, n, m] of P log-kernels [P, n, m] after `nr_sinkhorn_iter` sweeps (otgan_sinkhorn_plan_f32, the staged
+    entry point: matching.py:52-57).  lambda only scales the statistics the library reports beside the plans."""
+    K = log_kernels
+    if not K.is_cuda:
+        raise _lib.OtganError("matching needs CUDA (MI355X) tensors; there is no CPU fallback")
+    if K.dtype != torch.float32 or K.dim() != 3:
+        raise ValueError("sinkhorn_plans takes float32 [P, n, m] log-kernels")
+    K = K.detach().contiguous()
+    L = _lib.lib()
+    P, n, m = K.shape
+    plan, planT = torch.empty_like(K), torch.empty((P, m, n), dtype=torch.float32, device=K.device)
+    stats = torch.empty((P, 4), dtype=torch.float64, device=K.device)
+    ws = _workspace(max(L.otgan_sinkhorn_workspace_bytes(P, n, m), 256), K.device)
+    rc = L.otgan_sinkhorn_plan_f32(K.data_ptr(), P, n, m, int(nr_sinkhorn_iter), float(sinkhorn_lambda), plan.data_ptr(),
+                                   planT.data_ptr(), stats.data_ptr(), ws.data_ptr(), ws.numel(), _lib.stream_ptr())
+    _lib.check(rc, "otgan_sinkhorn_plan_f32")
+    return plan
+
+
 def get_matched_features_rows(features_a, features_b, sinkhorn_lambda, nr_sinkhorn_iter, row_begin,
                               row_count, log_kernels=None):
     """Two-batch matching over the full shard lists, producing only rows
